@@ -18,10 +18,18 @@ broadcast over xGMI puts a replica into every GPU's HBM, no collective on the se
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  `roofline` is the astar kernel: algorithmic bytes (SURVEY.md 8d
-B_exp, from the kernel's own counters) / its HIP-event duration; `cpu_baseline` is the CPU oracle
-(oracle/, "port") timed on a bounded sample of the same queries on the host's cores (one read-only map
-shared by all threads; a 1-thread figure -- the reference planner is single-threaded -- and an N-thread
-figure), and the sample doubles as a full-size parity check of the timed GPU results.
+B_exp, from the kernel's own counters) / its HIP-event duration.
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what the headline does not
+need: `cpu_baseline` is the CPU oracle (oracle/, "port") timed on a bounded sample of the same queries on the
+host's cores (one read-only map shared by all threads; a 1-thread figure -- the reference planner is
+single-threaded -- and an N-thread figure), and the sample doubles as a full-size parity check of the timed GPU
+results; `stream` is the streamed leg; the default 1-GPU C4-ACC line also carries the other BASELINE
+configurations (c2, c3, c5, lpa, plpa).
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64): per query of the stream
+the result row (status, cost, expansions, states, order hash, trajectory length) and, on one GPU, the trajectories.
+Every value is finite: the cost of a query without a path (+inf) is written as -1, and cost_finite says which.
 """
 
 import argparse
@@ -60,7 +68,13 @@ def parse_args(argv=None):
                     help="per-query expansion cap setMaxNum (default: 2 000 000 for acc = the BASELINE.md C3 cap, 20000 for jrk)")
     ap.add_argument("--slots", type=int, default=0)
     ap.add_argument("--max-nodes", type=int, default=0, help="mean states per query used to size the shared pools")
-    ap.add_argument("--cpu-seconds", type=float, default=14.0, help="CPU-baseline sample budget of the N-thread leg (0 disables both legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: CPU baseline + parity sample (--cpu-seconds 14), the streamed leg "
+                         "and, on the default 1-GPU C4-ACC line, the other BASELINE configurations (--extras)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; result rows per query, trajectories on one GPU)")
+    ap.add_argument("--cpu-seconds", type=float, default=None,
+                    help="CPU-baseline sample budget of the N-thread leg (0 disables both legs; default 14 with --full, else 0)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="host threads of the N-thread CPU leg (0 = all cores, at most 64)")
     ap.add_argument("--helpers", type=int, default=-1, help="helper workgroups per leading workgroup: -1 auto (4; 2 for the 125-input lattice), 0 off, 2..4")
     ap.add_argument("--help-reserved", type=int, default=-1, help="workgroups that only ever help (-1 auto)")
@@ -76,7 +90,7 @@ def parse_args(argv=None):
                     help="N > 1, strong scaling: skip the additional throughput phase (a 1024 x N query stream through the same sharded path)")
     ap.add_argument("--stream", type=int, default=-1,
                     help="N = 1, C4 batch: batches of the additional streamed leg (mplx_stream: two batches in flight on two lanes of the same map replica; "
-                         "every result compared with the blocking step's); -1 auto = max(steps, 6), 0 off")
+                         "every result compared with the blocking step's); -1 auto = max(steps, 6) with --full, else off; 0 off")
     ap.add_argument("--stream-depth", type=int, default=2, help="lanes of the streamed leg (each holds a batch's pools: two fit 288 GB at C4 size)")
     ap.add_argument("--stream-helper-limit", type=int, default=32,
                     help="streamed leg: workgroups of a batch that stay on as helpers once its queue is empty (the others leave their compute unit to the next batch)")
@@ -88,12 +102,20 @@ def parse_args(argv=None):
     ap.add_argument("--warmup-cap", type=int, default=0, help="warm-up steps run with this expansion cap (a long single query is warmed up on a prefix of its search)")
     ap.add_argument("--extras", type=int, default=-1,
                     help="the other BASELINE configurations as extra keys of the C4 line (c2, c3, c5, lpa: each with its own roofline, single-thread "
-                         "CPU baseline and parity check); -1 auto = on for the default 1-GPU C4-ACC line, 0 off, 1 on")
+                         "CPU baseline and parity check); -1 auto = on for the default 1-GPU C4-ACC line with --full, 0 off, 1 on")
     return ap.parse_args(argv)
 
 
 def main():
     args = parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.cpu_seconds is None:
+        args.cpu_seconds = 14.0 if args.full else 0.0
+    if args.stream < 0 and not args.full:
+        args.stream = 0
+    if args.dump_outputs and args.config != "c4":
+        raise SystemExit(f"--dump-outputs: not available for --config {args.config}")
     if args.config == "c5":
         print(json.dumps(c5.run(args)), flush=True)
         return
@@ -105,7 +127,7 @@ def main():
         return
     default_line = (args.gpus == 1 and not args.single and args.lattice == "acc" and args.map == 512 and args.max_expand == 0 and
                     args.queries == 1024 and args.cpu_seconds > 0 and os.environ.get("MPLX_BENCH_FORCE_DIST") != "1")
-    want_extras = args.extras == 1 or (args.extras < 0 and default_line)
+    want_extras = args.extras == 1 or (args.extras < 0 and args.full and default_line)
     if want_extras and args.stream < 0:
         args.stream = min(max(args.steps, 6), 12)  # (room for the extra configurations inside the driver's window)
     out = c4.run(args)

@@ -7,7 +7,44 @@ import time
 
 import numpy as np
 
-from .common import HBM_PEAK_GBS, ROOT, _log, algorithmic_bytes, cpu_baseline
+from .common import DUMP_LIMIT_BYTES, HBM_PEAK_GBS, ROOT, _log, algorithmic_bytes, cpu_baseline, write_outputs
+
+ROW_FIELDS = ("query", "status", "n_expanded", "n_nodes", "cost", "expand_hash_hi", "expand_hash_lo", "traj_len")  # mpl_ros_amd.dist.result_row
+
+
+def _dump_outputs(dirpath, rows, pl=None, local=None):
+    """--dump-outputs: the result rows of the last timed step in stream order (one array per field of dist.result_row) and, where
+    this process planned the rows itself (local: query -> its index in pl's last batch), every query's trajectory: primitive
+    coefficients / durations / actions and the states at the joints, concatenated, traj_offsets[q] .. traj_offsets[q + 1] being query
+    q's primitives (traj_waypoint_offsets likewise for its joints).  Every value written is finite.  Trajectories that would not fit the size limit are written for a fixed, seeded sample of the queries."""
+    R = np.array(sorted(rows, key=lambda r: r[0]), dtype=np.float64).reshape(-1, len(ROW_FIELDS))
+    out = {name: R[:, k] for k, name in enumerate(ROW_FIELDS)}
+    # a query without a path has cost +inf: written as -1 (costs are >= 0), with cost_finite 0 beside it
+    out["cost_finite"] = np.isfinite(R[:, 4]).astype(np.float64)
+    out["cost"] = np.where(np.isfinite(R[:, 4]), R[:, 4], -1.0)
+    if pl is not None and local is not None:
+        nq = len(R)
+        lens = R[:, 7].astype(np.int64) * (R[:, 1] == 0)
+        per_prim, per_wp = 8 * (3 * 6 + 2), 8 * 12  # coefficients, duration, action; pos, vel, acc, jrk of a joint
+        cost_of = lens * per_prim + (lens + 1) * per_wp * (lens > 0) + 8
+        budget = DUMP_LIMIT_BYTES - R.nbytes - 16 * (nq + 2)
+        keep = np.arange(nq)
+        if cost_of.sum() > budget:
+            order = np.random.default_rng(20250620).permutation(nq)
+            keep = np.sort(order[:int(np.searchsorted(np.cumsum(cost_of[order]), budget))])
+        coeffs, ts, acts, wps, offsets, wp_offsets = [], [], [], [], [0], [0]
+        for q in keep:
+            tr = pl.getTraj(local[int(R[q, 0])]) if lens[q] > 0 else None
+            prs = tr.getPrimitives() if tr is not None else []
+            coeffs += [p.coeff(i) for p in prs for i in range(3)]
+            ts += [p.t() for p in prs]
+            acts += list(tr.actions) if tr is not None else []
+            wps += [np.concatenate([w.pos, w.vel, w.acc, w.jrk]) for w in (tr.getWaypoints() if prs else [])]
+            offsets.append(offsets[-1] + len(prs))
+            wp_offsets.append(len(wps))
+        out.update({"traj_queries": R[keep, 0], "traj_offsets": np.array(offsets), "traj_waypoint_offsets": np.array(wp_offsets), "traj_coeffs": np.array(coeffs).reshape(-1, 3, 6),
+                    "traj_t": np.array(ts), "traj_actions": np.array(acts), "traj_waypoints": np.array(wps).reshape(-1, 12)})
+    write_outputs(dirpath, out)
 
 
 def _speculation(pl, results):
@@ -211,6 +248,9 @@ def run(args):
     if rank == 0:
         _log(f"timed steps done: {1e3 * elapsed / args.steps:.1f} ms per step")
     results, kernel_ms = state["results"], state["kernel_ms"]
+    if args.dump_outputs and rank == 0 and not multi:  # (before anything below re-plans or frees the pools)
+        _dump_outputs(args.dump_outputs, [mdist.result_row(qi, r.status, r.n_expanded, r.n_nodes, r.cost, r.expand_hash, r.traj_len) for qi, r in zip(mine, results)],
+                      pl, {qi: k for k, qi in enumerate(mine)})
     out = None
 
     n_exp = sum(r.n_expanded for r in results)
@@ -450,6 +490,11 @@ def run(args):
                 out["roofline"]["launch"] = "rank 0's share of the ONE-stream phase (out['strong']); the throughput phase launches the same kernel on 1024 queries per GPU"
         elif thr is not None:
             out["throughput"] = thr
+        if args.dump_outputs and multi:  # the rows of the phase the line's value is of, merged over the ranks (weak-only: rank 0's own)
+            rows = tmerged if (thr is not None and args.scaling == "weak") else state["merged"]
+            if rows is None:
+                rows = [mdist.result_row(qi, r.status, r.n_expanded, r.n_nodes, r.cost, r.expand_hash, r.traj_len) for qi, r in zip(mine, results)]
+            _dump_outputs(args.dump_outputs, rows)
     if multi:
         dist.barrier()
         dist.destroy_process_group()

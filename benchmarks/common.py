@@ -32,6 +32,24 @@ def algorithmic_bytes(control, n_expanded, voxel_reads, n_succ_finite):
     return n_expanded * s_in + voxel_reads + n_succ_finite * (s_out + s_probe)
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all arrays of one run together
+
+
+def write_outputs(dirpath, arrays):
+    """--dump-outputs: every array as dirpath/<name>.npy in float64, at most DUMP_LIMIT_BYTES in all, every value finite."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    bad = sorted(k for k, a in arrays.items() if not np.isfinite(a).all())
+    if bad:
+        raise RuntimeError(f"--dump-outputs: non-finite values in {', '.join(bad)}")
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirpath, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirpath, f"{k}.npy"), a)
+    _log(f"outputs written to {dirpath}: {', '.join(sorted(arrays))} ({total / 1e6:.1f} MB)")
+
+
 def _cpu_run(cfg, queries, order, budget_s, procs, caps=None):
     """`procs` worker PROCESSES (oracle/cpu_worker.py), one query at a time each, all mapping ONE read-only copy
     of the voxel map.  A dispatcher thread per worker hands out the next query of `order` until the budget is

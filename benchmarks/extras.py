@@ -27,9 +27,9 @@ def _compact(d, extra=()):
 
 
 def _child(argv, timeout_s):
-    """One leg as a process of its own (`python bench.py ...`): a leg that dies -- a device fault ends its process -- costs the line
+    """One leg as a process of its own (`python bench.py --full ...`): a leg that dies -- a device fault ends its process -- costs the line
     one key, not the line; its ONE JSON line is parsed from stdout."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + [str(a) for a in argv]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + [str(a) for a in argv]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if r.returncode != 0 or not lines:

@@ -284,15 +284,16 @@ def test_reference_planner_headers_compile_unchanged_against_the_shim(tmp_path):
 
 # ---------------------------------------------------------------- round 4: the reference's own multi-robot code on the device back-end
 REF_NODE = "/root/reference/mpl_test_node/src"
-MULTI_ROBOT_BIN = os.path.join(ROOT, "tests", "cpp", "_bin", "multi_robot_driver")
+# the drivers that compile reference sources are reference binaries: they live in oracle/_ref/ with the other ones
+MULTI_ROBOT_BIN = os.path.join(ROOT, "oracle", "_ref", "multi_robot_driver")
 
 
 def _build_ref_node_driver(binary, source):
     os.makedirs(os.path.dirname(binary), exist_ok=True)
     subprocess.check_call(["g++", "-O2", "-std=c++14", "-Wall", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "include", "mpl_shim"),
                            "-I" + REF_POLY, "-I" + os.path.join(ROOT, "tests", "cpp", "stubs"), "-I" + REF_NODE, "-o", binary,
-                           os.path.join(ROOT, "tests", "cpp", source), os.path.join(LIBDIR, "libmplx.so"),
-                           "-Wl,-rpath,$ORIGIN/../../../mpl_ros_amd/csrc"])
+                           os.path.join(ROOT, "tests", "cpp", source), "-L" + LIBDIR, "-lmplx",  # (by name: the runpath finds it wherever the tree lies)
+                           "-Wl,-rpath,$ORIGIN/../../mpl_ros_amd/csrc"])
 
 
 def build_multi_robot_driver():
@@ -303,7 +304,7 @@ def build_multi_robot_driver():
     _build_ref_node_driver(MULTI_ROBOT_BIN, "multi_robot_driver.cpp")
 
 
-POLY_REPLANNER_BIN = os.path.join(ROOT, "tests", "cpp", "_bin", "poly_map_replanner_driver")
+POLY_REPLANNER_BIN = os.path.join(ROOT, "oracle", "_ref", "poly_map_replanner_driver")
 
 
 def build_poly_replanner_driver():

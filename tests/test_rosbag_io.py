@@ -1,6 +1,7 @@
-"""The bag reader against the reference's surviving fixtures.  Needs /root/reference (build container
-only); the GPU box and CI without it skip -- the committed tests/golden/skir_map.npz is what travels."""
+"""The bag reader against the reference's surviving fixture: skir.bag, cut down to its /voxel_map topic
+(tests/golden/skir_voxel_map.bag.xz, written by tests/golden/make_skir_bag_fixture.py)."""
 import hashlib
+import lzma
 import os
 import struct
 
@@ -9,7 +10,6 @@ import pytest
 
 from mpl_ros_amd import rosbag_io
 
-REF = "/root/reference/mpl_test_node/maps"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -35,9 +35,10 @@ def test_reader_on_a_hand_built_bag(tmp_path):
     assert m["origin"] == (1.0, 2.0, 3.0) and m["dim"] == (4, 3, 2) and np.array_equal(m["data"], grid)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not present")
-def test_skir_bag_matches_the_committed_fixture():
-    m = rosbag_io.read_bag(os.path.join(REF, "skir", "skir.bag"), "voxel_map")[-1]
+def test_skir_bag_matches_the_committed_fixture(tmp_path):
+    bag = tmp_path / "skir.bag"
+    bag.write_bytes(lzma.decompress(open(os.path.join(ROOT, "tests", "golden", "skir_voxel_map.bag.xz"), "rb").read()))
+    m = rosbag_io.read_bag(str(bag), "voxel_map")[-1]
     d = np.load(os.path.join(ROOT, "tests", "golden", "skir_map.npz"))
     assert m["dim"] == tuple(d["grid"].shape[::-1]) and np.allclose(m["origin"], d["origin"]) and float(m["resolution"]) == pytest.approx(float(d["res"]))
     assert hashlib.sha256(m["data"].tobytes()).hexdigest() == str(d["sha256"])

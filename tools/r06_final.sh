@@ -20,7 +20,7 @@ suite)
   tail -3 $OUT/pytest_gpu.txt ;;
 bench)
   T0=$(date +%s)
-  timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
+  timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_default.json 2> $OUT/bench_default.err
   echo "bench wall $(( $(date +%s) - T0 )) s" | tee $OUT/bench_default.wall
   python - <<PY
 import json
@@ -64,9 +64,9 @@ prof)
   find "$OUT" -name "*.db" -delete
   python tools/make_traffic_json.py "$OUT/summary_block.txt" profiles/${TAG}_c4acc_blocking.txt "$OUT/summary_bulk.txt" > $OUT/traffic.json 2> $OUT/traffic.err; head -c 700 $OUT/traffic.json; echo ;;
 other)
-  timeout 100 python bench.py --config c5 --steps 3 --warmup 1 > $OUT/bench_c5.json 2> $OUT/bench_c5.err; head -c 300 $OUT/bench_c5.json; echo
-  timeout 60 python bench.py --config lpa --steps 2 --warmup 1 > $OUT/bench_lpa.json 2> $OUT/bench_lpa.err; head -c 300 $OUT/bench_lpa.json; echo
-  timeout 60 python bench.py --config plpa --steps 3 --warmup 1 > $OUT/bench_plpa.json 2> $OUT/bench_plpa.err; head -c 300 $OUT/bench_plpa.json; echo
+  timeout 100 python bench.py --config c5 --steps 3 --warmup 1 --full > $OUT/bench_c5.json 2> $OUT/bench_c5.err; head -c 300 $OUT/bench_c5.json; echo
+  timeout 60 python bench.py --config lpa --steps 2 --warmup 1 --full > $OUT/bench_lpa.json 2> $OUT/bench_lpa.err; head -c 300 $OUT/bench_lpa.json; echo
+  timeout 60 python bench.py --config plpa --steps 3 --warmup 1 --full > $OUT/bench_plpa.json 2> $OUT/bench_plpa.err; head -c 300 $OUT/bench_plpa.json; echo
   timeout 120 python bench.py --single --lattice jrk --steps 1 --warmup 1 --cpu-seconds 5 > $OUT/bench_c3.json 2> $OUT/bench_c3.err; head -c 300 $OUT/bench_c3.json; echo
   timeout 120 python bench.py --lattice jrk --steps 5 --warmup 2 --cpu-seconds 8 --stream 0 > $OUT/bench_c4jrk.json 2> $OUT/bench_c4jrk.err; head -c 300 $OUT/bench_c4jrk.json; echo
   # the C4-JRK batch at the survey's cap (2 000 000 per query): recycled pools of 48 leading workgroups, launches of 96 queries
