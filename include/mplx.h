@@ -506,6 +506,44 @@ const char *mplx_kernel_name(const mplx_ctx *ctx);
 uint64_t mplx_plan_epoch(const mplx_ctx *ctx);
 const char *mplx_version(void);
 
+/* ---- point-cloud planner (mpl_external_planner/.../ellipsoid_planner: EllipsoidPlanner + env_cloud + EllipsoidUtil, as
+ *      ellipsoid_planner_node.cpp:64-175 drives it).  The obstacles are a raw point cloud (no voxel map): a primitive is free
+ *      when its three bounding-box samples lie inside the box and no cloud point lies inside any of its ellipsoids (robot
+ *      radius r, height 0.1).  The cloud is indexed on the device.  Blocked primitives are skipped, not given cost +inf.
+ *      The search is PlannerBase::plan's A* (the start is always free; getExpandedNodes stays empty upstream). ---- */
+typedef struct mplx_cloud mplx_cloud;
+typedef struct {
+  double state[13];    /* tn: pos3 vel3 acc3 jrk3, t = curr.t + dt */
+  double cost;         /* J(control) + w dt; +inf when the primitive is skipped */
+  int32_t action;      /* index into U */
+  int32_t valid;       /* 0: skipped (tn == curr, validate_primitive failed, or EllipsoidUtil::isFree failed) */
+} mplx_cloud_succ;
+int mplx_cloud_create(int device, mplx_cloud **out);
+void mplx_cloud_destroy(mplx_cloud *c);
+const char *mplx_cloud_last_error(const mplx_cloud *c); /* c may be NULL: last create error */
+/* planner set-up: control kind (MPLX_VEL / ACC / JRK / SNP), control inputs U (n_u x 3, n_u <= 256), dt, limits, w */
+int mplx_cloud_config(mplx_cloud *c, int32_t control, int32_t n_u, const double *U, double dt, double v_max, double a_max, double j_max, double w);
+/* setMap(obs, r, ori, dim): uploads the n points (n x 3 doubles; n may be 0) and builds the cloud index on the device */
+int mplx_cloud_set_map(mplx_cloud *c, int32_t n, const double *pts, double r, const double ori[3], const double dim[3]);
+/* env_cloud::get_succ for K states (pos3 vel3 acc3 jrk3 t, 13 doubles each); out: K x n_u records, [k * n_u + i] for input i */
+int mplx_cloud_get_succ_batch(mplx_cloud *c, int32_t K, const double *states, mplx_cloud_succ *out);
+/* point tests (radius-filter candidates looked at) of the last get_succ_batch */
+uint64_t mplx_cloud_last_point_tests(const mplx_cloud *c);
+int mplx_cloud_set_capacity(mplx_cloud *c, int32_t n_slots, uint64_t total_nodes, uint64_t total_edges, uint64_t total_open_log);
+/* PlannerBase::plan for n queries in ONE launch on the one cloud, one workgroup per query: starts / goals are 13 doubles each
+ * (pos3 vel3 acc3 jrk3 t; the goal's control kind is the planner's).  mplx_result.voxel_reads counts point tests. */
+int mplx_cloud_plan_batch(mplx_cloud *c, int32_t n, const double *starts, const double *goals, double eps, double tol_pos, double tol_vel,
+                          double tol_acc, int32_t max_expand, int32_t heur_ignore_dynamics, mplx_result *out);
+/* trajectory of query q of the last batch: wps[traj_len + 1], actions[traj_len], node_ids[traj_len + 1]; NULLs allowed */
+int mplx_cloud_result_traj(mplx_cloud *c, int32_t q, mplx_waypoint *wps, int32_t *actions, int32_t *node_ids);
+/* the state space of query q of the last batch (getCloseSet / getOpenSet): n_nodes states in id order with g and their
+ * closed / opened flags (a state in OPEN is opened and not closed) */
+int mplx_cloud_result_nodes(mplx_cloud *c, int32_t q, uint64_t cap, mplx_waypoint *coords, double *g, int32_t *closed, int32_t *opened);
+int mplx_cloud_set_record(mplx_cloud *c, uint32_t cap_per_query);
+int mplx_cloud_result_expanded(mplx_cloud *c, int32_t q, uint32_t cap, int32_t *ids, uint32_t *n);
+int mplx_cloud_set_deadline(mplx_cloud *c, double seconds); /* launch guard of the search (mplx_set_deadline) */
+int mplx_cloud_last_kernel_ms(const mplx_cloud *c, float *ms);
+
 /* ---- after the search: refinement and sampling (host arithmetic, no context, no device) ----
  * TrajSolver3D(control).setWaypoints(wps).setDts(dts).solve(), map_planner_node.cpp:217-227: minimum-derivative
  * piecewise polynomial through n_wp waypoints (control kind VEL / ACC / JRK: minimum velocity / acceleration / jerk);

@@ -49,6 +49,10 @@ class Result(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class CloudSucc(C.Structure):  # mplx_cloud_succ
+    _fields_ = [("state", C.c_double * 13), ("cost", C.c_double), ("action", C.c_int32), ("valid", C.c_int32)]
+
+
 EXPORTS = [
     "mplx_ctx_create", "mplx_ctx_destroy", "mplx_last_error", "mplx_set_stream",
     "mplx_map_set", "mplx_map_set_device", "mplx_map_free_unknown", "mplx_map_get", "mplx_map_info", "mplx_map_query",
@@ -74,6 +78,9 @@ EXPORTS = [
     "mplx_set_deadline", "mplx_set_pool_recycling", "mplx_debug_hang_next_launch", "mplx_debug_query_records",
     "mplx_stream_create", "mplx_stream_destroy", "mplx_stream_last_error", "mplx_stream_depth", "mplx_stream_configure",
     "mplx_stream_submit", "mplx_stream_done", "mplx_stream_wait",
+    "mplx_cloud_create", "mplx_cloud_destroy", "mplx_cloud_last_error", "mplx_cloud_config", "mplx_cloud_set_map", "mplx_cloud_get_succ_batch",
+    "mplx_cloud_last_point_tests", "mplx_cloud_set_capacity", "mplx_cloud_plan_batch", "mplx_cloud_result_traj", "mplx_cloud_result_nodes",
+    "mplx_cloud_set_record", "mplx_cloud_result_expanded", "mplx_cloud_set_deadline", "mplx_cloud_last_kernel_ms",
 ]
 
 
@@ -254,5 +261,24 @@ def load():
     L.mplx_stream_submit.argtypes = [P, C.c_int, C.POINTER(Waypoint), C.POINTER(Waypoint), C.POINTER(C.c_int64)]
     L.mplx_stream_done.argtypes = [P, C.c_int64]
     L.mplx_stream_wait.argtypes = [P, C.c_int64, C.POINTER(Result), C.POINTER(P)]
+    L.mplx_cloud_create.argtypes = [C.c_int, C.POINTER(P)]
+    L.mplx_cloud_destroy.argtypes = [P]
+    L.mplx_cloud_destroy.restype = None
+    L.mplx_cloud_last_error.argtypes = [P]
+    L.mplx_cloud_last_error.restype = C.c_char_p
+    L.mplx_cloud_config.argtypes = [P, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]
+    L.mplx_cloud_set_map.argtypes = [P, C.c_int32, C.c_void_p, C.c_double, D2, D2]
+    L.mplx_cloud_get_succ_batch.argtypes = [P, C.c_int32, C.c_void_p, C.POINTER(CloudSucc)]
+    L.mplx_cloud_last_point_tests.argtypes = [P]
+    L.mplx_cloud_last_point_tests.restype = C.c_uint64
+    L.mplx_cloud_set_capacity.argtypes = [P, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.mplx_cloud_plan_batch.argtypes = [P, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                        C.POINTER(Result)]
+    L.mplx_cloud_result_traj.argtypes = [P, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mplx_cloud_result_nodes.argtypes = [P, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mplx_cloud_set_record.argtypes = [P, C.c_uint32]
+    L.mplx_cloud_result_expanded.argtypes = [P, C.c_int32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.mplx_cloud_set_deadline.argtypes = [P, C.c_double]
+    L.mplx_cloud_last_kernel_ms.argtypes = [P, C.POINTER(C.c_float)]
     _lib = L
     return L

@@ -1962,3 +1962,4 @@ extern "C" int mplx_last_kernel_ms(const mplx_ctx *c, float *ms) {
 #include "mplx_grid.inl"
 #include "mplx_poly_search.h"
 #include "mplx_poly.inl"
+#include "mplx_ctx_ext.inl"

@@ -1,0 +1,286 @@
+"""CPU checker of the point-cloud planner: an independent restatement of env_cloud + EllipsoidUtil
+(mpl_external_planner/.../ellipsoid_planner/env_cloud.h:50-70, ellipsoid_util.h:62-90, primitive_ellipsoid_utils.h:17-51)
+and of the A* loop around it, in the evaluation order of the E-list (mpl_ros_amd/csrc/mplx_cloud.h).
+
+Primitive build / evaluate / max_vel / validate / J, the state key, the heuristic and the goal test come from the CPU
+restatement of the voxel path (oracle/orc.py).  The point test is done here with a plain host grid (every point within
+two radii of a sample centre is looked at), not with the product's index.  Test infrastructure only.
+"""
+import ctypes as C
+import heapq
+import math
+
+import numpy as np
+
+from oracle import orc
+
+H_AXE = 0.1
+BBOX_EPS = 1e-10
+
+
+def bbox_planes(ori, dim):
+    """setBoundingBox: six Hyperplane3D(point, normal), in the reference's order and arithmetic"""
+    o, d = [float(x) for x in ori], [float(x) for x in dim]
+    h0, h1, h2 = d[0] / 2, d[1] / 2, d[2] / 2
+    q = [(o[0] + 0.0, o[1] + h1, o[2] + h2), (o[0] + h0, o[1] + 0.0, o[2] + h2), (o[0] + h0, o[1] + h2, o[2] + 0.0),
+         ((o[0] + d[0]) - 0.0, (o[1] + d[1]) - h1, (o[2] + d[2]) - h2), ((o[0] + d[0]) - h0, (o[1] + d[1]) - 0.0, (o[2] + d[2]) - h2),
+         ((o[0] + d[0]) - h0, (o[1] + d[1]) - h1, (o[2] + d[2]) - 0.0)]
+    n = [(-1.0, -0.0, -0.0), (-0.0, -1.0, -0.0), (-0.0, -0.0, -1.0), (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0)]
+    return list(zip(q, n))
+
+
+def in_bbox(planes, p):
+    for q, n in planes:
+        if (n[0] * (p[0] - q[0]) + n[1] * (p[1] - q[1])) + n[2] * (p[2] - q[2]) > BBOX_EPS:
+            return False
+    return True
+
+
+def _normalize(v):
+    z = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]
+    if z > 0.0:
+        s = math.sqrt(z)
+        return [v[0] / s, v[1] / s, v[2] / s]
+    return list(v)
+
+
+def _cross(a, b):
+    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+
+def ellipsoid_C(axe, acc):
+    """generate_ellipsoid (E5): C = R diag(axe) R^T, R = [b1 b2 b3]"""
+    b3 = _normalize([acc[0] + 0.0, acc[1] + 0.0, acc[2] + 9.81])
+    b2 = _normalize(_cross(b3, [1.0, 0.0, 0.0]))
+    b1 = _normalize(_cross(b2, b3))
+    R = [[b1[i], b2[i], b3[i]] for i in range(3)]
+    D = [[axe[0], 0.0, 0.0], [0.0, axe[1], 0.0], [0.0, 0.0, axe[2]]]
+    M = [[(R[i][0] * D[0][j] + R[i][1] * D[1][j]) + R[i][2] * D[2][j] for j in range(3)] for i in range(3)]
+    return [[(M[i][0] * R[j][0] + M[i][1] * R[j][1]) + M[i][2] * R[j][2] for j in range(3)] for i in range(3)], (b1, b2, b3)
+
+
+def inverse3(m):
+    """Eigen's 3x3 cofactor inverse (E4)"""
+    cof = [[0.0] * 3 for _ in range(3)]
+    for i in range(3):
+        for j in range(3):
+            i1, i2, j1, j2 = (i + 1) % 3, (i + 2) % 3, (j + 1) % 3, (j + 2) % 3
+            cof[i][j] = m[i1][j1] * m[i2][j2] - m[i1][j2] * m[i2][j1]
+    det = (cof[0][0] * m[0][0] + cof[1][0] * m[1][0]) + cof[2][0] * m[2][0]
+    invdet = 1.0 / det
+    return [[cof[j][i] * invdet for j in range(3)] for i in range(3)]
+
+
+def inside(ci, d, pts):
+    """E3 for an (n, 3) float64 array of points: ||C^-1 (p - d)|| <= 1"""
+    v0, v1, v2 = pts[:, 0] - d[0], pts[:, 1] - d[1], pts[:, 2] - d[2]
+    y0 = (ci[0][0] * v0 + ci[0][1] * v1) + ci[0][2] * v2
+    y1 = (ci[1][0] * v0 + ci[1][1] * v1) + ci[1][2] * v2
+    y2 = (ci[2][0] * v0 + ci[2][1] * v1) + ci[2][2] * v2
+    return np.sqrt((y0 * y0 + y1 * y1) + y2 * y2) <= 1.0
+
+
+class Cloud:
+    """EllipsoidUtil(r) with setObstacles(obs) (every point kept: the box has no planes yet) and setBoundingBox(ori, dim)"""
+
+    def __init__(self, obs, r, ori, dim):
+        self.pd = np.ascontiguousarray(np.asarray(obs, dtype=np.float64).reshape(-1, 3))
+        self.pf = self.pd.astype(np.float32)
+        self.r = float(r)
+        self.rf = np.float32(self.r)
+        self.r2f = np.float32(float(self.rf) * float(self.rf))
+        self.axe = (self.r, self.r, H_AXE)
+        self.planes = bbox_planes(ori, dim)
+        self.tests = 0
+        # host grid of edge 2 r over the float coordinates: a point the filter accepts is within r (1 + 2^-20) of the centre
+        self.cell = 2.0 * float(self.rf)
+        self.grid = {}
+        if len(self.pd):
+            keys = np.floor(self.pf.astype(np.float64) / self.cell).astype(np.int64)
+            order = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
+            ks = keys[order]
+            cut = np.flatnonzero(np.any(np.diff(ks, axis=0) != 0, axis=1)) + 1
+            for a, b in zip(np.r_[0, cut], np.r_[cut, len(order)]):
+                self.grid[tuple(ks[a])] = order[a:b]
+
+    def candidates(self, cf):
+        c = [math.floor(float(x) / self.cell) for x in cf]
+        idx = [self.grid.get((c[0] + i, c[1] + j, c[2] + k)) for i in (-1, 0, 1) for j in (-1, 0, 1) for k in (-1, 0, 1)]
+        idx = [a for a in idx if a is not None]
+        return np.concatenate(idx) if idx else np.zeros(0, dtype=np.int64)
+
+    def blocked_at(self, d, acc):
+        """one ellipsoid sample: E2 radius filter in float32, E3 inside test in float64"""
+        if len(self.pd) == 0:  # E7
+            return False
+        cf = np.array(d, dtype=np.float64).astype(np.float32)
+        idx = self.candidates(cf)
+        if len(idx) == 0:
+            return False
+        self.tests += len(idx)
+        pf = self.pf[idx]
+        dx, dy, dz = pf[:, 0] - cf[0], pf[:, 1] - cf[1], pf[:, 2] - cf[2]
+        dist = (dx * dx + dy * dy) + dz * dz
+        cand = idx[dist < self.r2f]
+        if len(cand) == 0:
+            return False
+        Cm, _ = ellipsoid_C(self.axe, acc)
+        return bool(np.any(inside(inverse3(Cm), d, self.pd[cand])))
+
+    def is_free(self, pr, dt):
+        """EllipsoidUtil::isFree(pr): E1 then E6"""
+        L = orc.lib()
+        w = orc.Waypoint()
+        h = dt / 2
+        for i in range(3):
+            L.orc_primitive_evaluate(C.byref(pr), i * h, C.byref(w))
+            if not in_bbox(self.planes, list(w.pos)):
+                return False
+        mv = 0.0
+        for k in range(3):
+            v = L.orc_primitive_max_vel(C.byref(pr), k)
+            mv = v if v > mv else mv
+        n = int(math.ceil(mv * dt / self.axe[0]))
+        for j in range(n + 1):
+            t = 0.0 if n == 0 else j * (dt / n)
+            L.orc_primitive_evaluate(C.byref(pr), t, C.byref(w))
+            if self.blocked_at(list(w.pos), list(w.acc)):
+                return False
+        return True
+
+
+def state_wp(s, control):
+    s = [float(x) for x in s]
+    return orc.waypoint(s[0:3], s[3:6], s[6:9], s[9:12], control=control, t=s[12])
+
+
+def wp_state13(w):
+    return np.array(list(w.pos) + list(w.vel) + list(w.acc) + list(w.jrk) + [w.t], dtype=np.float64)
+
+
+def key_of(w):
+    k = (C.c_int32 * 16)()
+    n = orc.lib().orc_waypoint_key(C.byref(w), k)
+    return tuple(k[:n])
+
+
+class Checker:
+    """env_cloud::get_succ and PlannerBase::plan (A*) on the CPU"""
+
+    def __init__(self, cloud, control, U, dt, v_max=-1.0, a_max=-1.0, j_max=-1.0, w=10.0):
+        self.cloud, self.control = cloud, control
+        self.U = np.ascontiguousarray(np.asarray(U, dtype=np.float64).reshape(-1, 3))
+        self.dt, self.v_max, self.a_max, self.j_max, self.w = float(dt), v_max, a_max, j_max, w
+        self.mask = np.array([1.0] * 3 + [1.0 if control & 2 else 0.0] * 3 + [1.0 if control & 4 else 0.0] * 3 +
+                             [1.0 if control & 8 else 0.0] * 3 + [1.0])
+
+    def get_succ(self, s13):
+        """one record per input: (valid, successor state13, cost, action) -- E8"""
+        L = orc.lib()
+        cw = state_wp(s13, self.control)
+        ck = key_of(cw)
+        out = []
+        for i, u in enumerate(self.U):
+            pr = orc.Primitive()
+            L.orc_primitive_build(C.byref(cw), (C.c_double * 3)(*u), self.dt, C.byref(pr))
+            tn = orc.Waypoint()
+            L.orc_primitive_evaluate(C.byref(pr), self.dt, C.byref(tn))
+            tn.control = self.control
+            ok = key_of(tn) != ck and L.orc_validate_primitive(C.byref(pr), self.v_max, self.a_max, self.j_max) and self.cloud.is_free(pr, self.dt)
+            st = wp_state13(tn)
+            st[12] = float(s13[12]) + self.dt
+            cost = L.orc_primitive_J(C.byref(pr), self.control) + self.w * self.dt if ok else math.inf
+            out.append((bool(ok), st, cost, i))
+        return out
+
+    def plan(self, start, goal, eps=1.0, tol_pos=0.5, tol_vel=-1.0, tol_acc=-1.0, max_num=-1, heur_ignore_dynamics=False):
+        """A* with order (f, g, id) (D5), a closed state that improves re-opened (D6), max_num; the start is always free"""
+        P = orc.Planner()
+        P.set_config(self.control, self.U, dt=self.dt, v_max=self.v_max, a_max=self.a_max, j_max=self.j_max, w=self.w, eps=eps,
+                     tol_pos=tol_pos, tol_vel=tol_vel, tol_acc=tol_acc, max_expand=max_num, heur_ignore_dynamics=heur_ignore_dynamics)
+        gw = state_wp(goal, self.control)
+        P.set_goal(gw)
+        sw = state_wp(start, self.control)
+        res = {"status": 0, "cost": math.inf, "expanded": [], "states": [], "g": [], "closed": [], "traj": None}
+        if P.is_goal(sw):
+            res["cost"] = 0.0
+            return res
+        states, g, h, closed, opened, preds = [], [], [], [], [], []
+        table = {}
+
+        def create(s13, w):
+            table[key_of(w)] = len(states)
+            states.append(s13); g.append(math.inf); closed.append(False); opened.append(False); preds.append([])
+            h.append(0.0 if eps == 0 else P.heuristic(w))
+            return len(states) - 1
+
+        sid = create(np.array(start, dtype=np.float64) * self.mask, sw)
+        g[sid], opened[sid] = 0.0, True
+        heap = [(g[sid] + eps * h[sid], 0.0, sid)]
+        n_reopen = 0
+        n_open = 1  # states opened and not closed (the live entries of a decrease-key heap)
+        it = 0
+        status = 0
+        while True:
+            it += 1
+            while True:  # pop, dropping stale entries
+                f, gg, cur = heapq.heappop(heap)
+                if not closed[cur] and gg == g[cur]:
+                    break
+            closed[cur] = True
+            n_open -= 1
+            res["expanded"].append(cur)
+            for ok, st, cost, a in self.get_succ(states[cur]):
+                if not ok:
+                    continue
+                st = st * self.mask  # (a state keeps the derivatives its control kind carries)
+                w = state_wp(st, self.control)
+                k = key_of(w)
+                sid2 = table.get(k)
+                if sid2 is None:
+                    sid2 = create(st, w)
+                preds[sid2].append((cur, a, cost))  # (arrival order: on an exact tie recoverTraj keeps the oldest record)
+                tent = g[cur] + cost
+                if tent < g[sid2]:
+                    if closed[sid2]:
+                        n_reopen += 1  # D6
+                    if closed[sid2] or not opened[sid2]:
+                        n_open += 1
+                    g[sid2] = tent
+                    closed[sid2] = False
+                    opened[sid2] = True
+                    heapq.heappush(heap, (tent + eps * h[sid2], tent, sid2))
+            if P.is_goal(state_wp(states[cur], self.control)):
+                break
+            if max_num > 0 and it >= max_num:
+                status = 3
+                break
+            if n_open == 0:
+                status = 1
+                break
+        res.update(status=status, states=states, g=g, closed=closed, opened=opened, n_reopen=n_reopen)
+        if status != 0:
+            return res
+        node, nodes, acts = cur, [cur], []
+        while preds[node]:
+            best, mr, mg = None, math.inf, math.inf
+            for par, a, c in preds[node]:
+                rhs = g[par] + c
+                if rhs < mr or (rhs == mr and mg < g[par]):
+                    best, mr, mg = (par, a), rhs, g[par]
+            node = best[0]
+            acts.append(best[1])
+            nodes.append(node)
+            if node == sid:
+                break
+        nodes.reverse(), acts.reverse()
+        res["cost"] = g[cur]
+        res["traj"] = {"node_ids": nodes, "actions": acts, "states": np.array([states[i] for i in nodes])}
+        return res
+
+
+def expand_hash(ids):
+    h = 0
+    for i in ids:
+        h = (h * 0x100000001B3 + (i + 1)) & 0xFFFFFFFFFFFFFFFF
+    return h
