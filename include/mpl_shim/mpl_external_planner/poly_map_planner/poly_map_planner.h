@@ -14,7 +14,9 @@
  * setters keep a copy of the obstacles next to handing them to the reference's PolyMapUtil (which still answers
  * getPolyhedrons / getBoundingBox / getLinearObstacles and is what ENV_ wraps), and plan() uploads them as ONE world of
  * an mplx_poly object and runs PlannerBase::plan there (time-keyed states, env_poly_map.h:63-64; cost
- * J + 0.001 J(VEL) + w dt, :71-73).  2-D only, like every in-tree caller (multi_robot_node.cpp, poly_map_planner_node.cpp).
+ * J + 0.001 J(VEL) + w dt, :71-73).  2-D like every in-tree caller (multi_robot_node.cpp, poly_map_planner_node.cpp); a
+ * PolyMapPlanner3D (poly_map_planner.h:107, robot.hpp:229) plans through mplx_poly3_* instead, by way of the reference-free
+ * plumbing of poly3_device.h, and serves getCloseSet / getOpenSet / getExpandedNodes from the device (3-D LPA* is refused).
  * With setLPAstar(true) (poly_map_replanner_node.cpp:352) the planner keeps a device-resident LPA* state space of its own
  * (mplx_plpa_*): updateNodes() (:61-93) re-tests every stored predecessor primitive against the obstacles as they are now and
  * fills getBlockedPrimitives / getClearedPrimitives, plan() repairs, getSubStateSpace(k) re-roots (round 6).
@@ -25,6 +27,8 @@
 #include <mpl_external_planner/poly_map_planner/env_poly_map.h>  // the reference's own (next on the include path)
 #include <mpl_planner/common/planner_base.h>
 #include <mplx.h>
+
+#include "poly3_device.h"
 
 #include <vector>
 
@@ -84,6 +88,7 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
   void updateNodes() {
     blocked_prs_.clear();
     cleared_prs_.clear();
+    if (Dim == 3) { refuse3("updateNodes()"); return; }
     if (!lpa_ || !mplx_plpa_initialized(lpa_)) return;  // (if (!this->ss_ptr_) return;)
     mplx_poly *p = shared_poly_device();
     if (!p || !upload(p, lpa_control_)) return;
@@ -109,6 +114,7 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
   /// PlannerBase::initialized() / getSubStateSpace(time_step) of the LPA* planner (poly_map_replanner_node.cpp:231)
   bool initialized() { return lpa_ && mplx_plpa_initialized(lpa_); }
   void getSubStateSpace(int time_step) {
+    if (Dim == 3) { refuse3("getSubStateSpace()"); return; }
     if (!lpa_ || !mplx_plpa_initialized(lpa_)) return;
     mplx_poly *p = shared_poly_device();
     if (!p || !upload(p, lpa_control_)) return;
@@ -123,6 +129,7 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
     this->traj_ = Trajectory<Dim>();
     this->traj_cost_ = std::numeric_limits<decimal_t>::infinity();
     res_ = mplx_result();
+    if (Dim == 3 && has_map_) return plan3(start, goal);
     if (Dim != 2 || !has_map_) {
       printf(ANSI_COLOR_RED "[PolyMapPlanner] plan() refused: the mplx back-end plans 2-D moving-obstacle searches after setMap()\n" ANSI_COLOR_RESET);
       return false;
@@ -172,8 +179,119 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
   }
   const mplx_result &getResult() const { return res_; }
   size_t getExpandedNum() const { return (size_t)res_.n_expanded; }
+  /// setLPAstar(true) on a 3-D planner is refused (there is no 3-D LPA* on the device): plan() then fails
+  void setLPAstar(bool use_lpastar) {
+    if (Dim == 3 && use_lpastar) refuse3("setLPAstar(true)");
+    Base::setLPAstar(use_lpastar);
+  }
+  /// the state space / expansion order of the last 3-D plan, from the device (2-D: PlannerBase's)
+  vec_Vecf<Dim> getCloseSet() const override { return Dim == 3 ? set3(1) : Base::getCloseSet(); }
+  vec_Vecf<Dim> getOpenSet() const override { return Dim == 3 ? set3(0) : Base::getOpenSet(); }
+  vec_Vecf<Dim> getExpandedNodes() const override {
+    if (Dim != 3) return Base::getExpandedNodes();
+    vec_Vecf<Dim> ps;
+    for (int32_t id : plan3_.expanded) ps.push_back(pos3((size_t)id));
+    return ps;
+  }
 
  protected:
+  void refuse3(const char *what) const {
+    printf(ANSI_COLOR_RED "[PolyMapPlanner] %s refused: the mplx back-end has no 3-D LPA* (PolyMapPlanner3D plans with A* only)\n" ANSI_COLOR_RESET, what);
+  }
+  Vecf<Dim> pos3(size_t id) const {
+    Vecf<Dim> p;
+    for (int k = 0; k < Dim && k < 3; k++) p(k) = plan3_.node_pos[3 * id + (size_t)k];
+    return p;
+  }
+  vec_Vecf<Dim> set3(int closed) const {  // closed states, or the states in OPEN (opened and not closed)
+    vec_Vecf<Dim> ps;
+    for (size_t i = 0; i < plan3_.closed.size(); i++)
+      if (closed ? plan3_.closed[i] != 0 : (plan3_.opened[i] != 0 && plan3_.closed[i] == 0)) ps.push_back(pos3(i));
+    return ps;
+  }
+  static void planes3(const Polyhedron<Dim> &poly, std::vector<double> &hp) {  // n_hp x {px, py, pz, nx, ny, nz}
+    hp.clear();
+    for (const auto &v : poly.hyperplanes()) {
+      for (int k = 0; k < 3; k++) hp.push_back(k < Dim ? v.p_(k) : 0.0);
+      for (int k = 0; k < 3; k++) hp.push_back(k < Dim ? v.n_(k) : 0.0);
+    }
+  }
+  template <class V>
+  static void put3(const V &x, double *o) { for (int k = 0; k < 3; k++) o[k] = k < Dim ? x(k) : 0.0; }
+  /// plan() of a 3-D planner: the world as the setters received it, planned through poly3_device.h; getTraj from the parent
+  /// state and action of every step, as the 2-D path builds it
+  bool plan3(const Waypoint<Dim> &start, const Waypoint<Dim> &goal) {
+    plan3_ = mplx_shim::Poly3Plan();
+    if (this->use_lpastar_) {
+      refuse3("plan() with setLPAstar(true)");
+      return false;
+    }
+    mplx_shim::Poly3Query q;
+    q.control = (int)start.control & 15;
+    for (const auto &u : this->U_vec_)
+      for (int k = 0; k < 3; k++) q.U.push_back(k < Dim && k < (int)u.rows() ? u(k) : 0.0);
+    q.dt = this->dt_; q.v_max = this->v_max_; q.a_max = this->a_max_; q.j_max = this->j_max_; q.w = this->w_;
+    put3(ori_, q.ori);
+    put3(dim_, q.dim);
+    q.start_t = start_t_;
+    for (const auto &o : static_obs_) {
+      mplx_shim::Poly3Obstacle d;
+      d.kind = 0;
+      planes3(o.geometry(), d.hp);
+      put3(o.p(), d.p);
+      q.obstacles.push_back(d);
+    }
+    for (const auto &o : linear_obs_) {
+      mplx_shim::Poly3Obstacle d;
+      d.kind = 1;
+      planes3(o.geometry(), d.hp);
+      put3(o.p(), d.p);
+      put3(o.v(), d.v);
+      d.cov_v = o.cov_v();
+      q.obstacles.push_back(d);
+    }
+    for (const auto &o : nonlinear_obs_) {
+      mplx_shim::Poly3Obstacle d;
+      d.kind = 2;
+      planes3(o.geometry(), d.hp);
+      for (const auto &pr : o.traj().getPrimitives()) {  // n_seg x {cx[6], cy[6], cz[6], T}
+        for (int ax = 0; ax < 3; ax++) {
+          const Vec6f c = ax < Dim ? pr.pr(ax).coeff() : Vec6f();
+          for (int k = 0; k < 6; k++) d.segs.push_back(c(k));
+        }
+        d.segs.push_back(pr.t());
+      }
+      d.start_t = o.start_t();
+      d.dis_front = o.disappear_front_;
+      d.dis_back = o.disappear_back_;
+      q.obstacles.push_back(d);
+    }
+    put3(start.pos, q.start); put3(start.vel, q.start + 3); put3(start.acc, q.start + 6); put3(start.jrk, q.start + 9);
+    q.start[12] = start.t;
+    put3(goal.pos, q.goal); put3(goal.vel, q.goal + 3); put3(goal.acc, q.goal + 6); put3(goal.jrk, q.goal + 9);
+    q.eps = this->epsilon_; q.tol_pos = this->tol_pos_; q.tol_vel = this->tol_vel_;
+    q.max_num = this->max_num_;
+    q.heur_ignore_dynamics = this->heur_ignore_dynamics_ ? 1 : 0;
+    if (!mplx_shim::poly3_plan(q, plan3_)) return false;
+    res_ = plan3_.res;
+    if (res_.status == MPLX_PLAN_START_OCCUPIED) { printf(ANSI_COLOR_RED "[PlannerBase] start is not free!\n" ANSI_COLOR_RESET); return false; }
+    this->traj_cost_ = res_.cost;
+    if (res_.status != MPLX_PLAN_OK || std::isinf(res_.cost)) {
+      printf(ANSI_COLOR_RED "[MPPlanner] Cannot find a traj! (status %d)\n" ANSI_COLOR_RESET, res_.status);
+      this->traj_cost_ = std::numeric_limits<decimal_t>::infinity();
+      return false;
+    }
+    vec_E<Primitive<Dim>> prs;
+    for (size_t i = 0; i < plan3_.actions.size(); i++) {
+      Waypoint<Dim> w(start.control);
+      const double *s = &plan3_.states[i * 13];
+      for (int k = 0; k < Dim && k < 3; k++) { w.pos(k) = s[k]; w.vel(k) = s[3 + k]; w.acc(k) = s[6 + k]; w.jrk(k) = s[9 + k]; }
+      w.t = s[12];
+      prs.push_back(Primitive<Dim>(w, this->U_vec_[(size_t)plan3_.actions[i]], this->dt_));
+    }
+    this->traj_ = Trajectory<Dim>(prs);
+    return true;
+  }
   static std::vector<double> planes(const Polyhedron<Dim> &poly) {  // n_hp x {px, py, nx, ny}
     std::vector<double> hp;
     for (const auto &v : poly.hyperplanes()) { hp.push_back(v.p_(0)); hp.push_back(v.p_(1)); hp.push_back(v.n_(0)); hp.push_back(v.n_(1)); }
@@ -266,6 +384,7 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
   mplx_result res_ = mplx_result();
   mplx_plpa *lpa_ = nullptr;  // the LPA* state space of this planner (setLPAstar(true)), created by its first plan()
   int32_t lpa_control_ = MPLX_ACC;
+  mplx_shim::Poly3Plan plan3_;  // what the last 3-D plan left on the host (trajectory, state space, expansion order)
 };
 
 typedef PolyMapPlanner<2> PolyMapPlanner2D;

@@ -544,6 +544,44 @@ int mplx_cloud_result_expanded(mplx_cloud *c, int32_t q, uint32_t cap, int32_t *
 int mplx_cloud_set_deadline(mplx_cloud *c, double seconds); /* launch guard of the search (mplx_set_deadline) */
 int mplx_cloud_last_kernel_ms(const mplx_cloud *c, float *ms);
 
+/* ---- moving-obstacle environment in 3-D: PolyMapPlanner3D (poly_map_planner.h:107) over env_poly_map<3> / PolyMapUtil<3> /
+ *      collide<3> (poly_map_util.h:52-109, primitive_geometry_utils.h, simple_obstacle.h).  mplx_poly_* one for one, with
+ *      3-D worlds: a bounding box of six faces, hyperplanes n_hp x {px, py, pz, nx, ny, nz}, trajectory segments
+ *      n_seg x {cx[6], cy[6], cz[6], T}, states of 13 doubles (pos3 vel3 acc3 jrk3 t).  get_succ: any control kind; the
+ *      search: ACC or JRK states, one workgroup per query, many queries (each in its own world) in one launch. ---- */
+typedef struct mplx_poly3 mplx_poly3;
+typedef struct {
+  double state[13];    /* tn: pos3 vel3 acc3 jrk3, t = curr.t + dt */
+  double cost;         /* J(control) + 0.001 J(VEL) + w dt, or +inf when isFree(pr, t) fails */
+  int32_t action;      /* index into U */
+  int32_t valid;       /* 0: skipped (end point outside the bounding box, or validate_primitive failed) */
+} mplx_poly3_succ;
+int mplx_poly3_create(int device, mplx_poly3 **out);
+void mplx_poly3_destroy(mplx_poly3 *p);
+const char *mplx_poly3_last_error(const mplx_poly3 *p); /* p may be NULL: last create error */
+/* planner set-up: control kind (MPLX_VEL / ACC / JRK / SNP), control inputs U (n_u x 3, n_u <= 32), dt, limits, w */
+int mplx_poly3_config(mplx_poly3 *p, int32_t control, int32_t n_u, const double *U, double dt, double v_max, double a_max, double j_max, double w);
+int mplx_poly3_begin(mplx_poly3 *p, int32_t n_worlds);
+int mplx_poly3_set_world(mplx_poly3 *p, int32_t world, const double ori[3], const double dim[3], double start_t);
+int mplx_poly3_add_static(mplx_poly3 *p, int32_t world, int32_t n_hp, const double *hp, const double pt[3]);
+int mplx_poly3_add_linear(mplx_poly3 *p, int32_t world, int32_t n_hp, const double *hp, const double pt[3], const double v[3], double cov_v);
+int mplx_poly3_add_nonlinear(mplx_poly3 *p, int32_t world, int32_t n_hp, const double *hp, int32_t n_seg, const double *segs, double start_t, int32_t dis_front, int32_t dis_back);
+int mplx_poly3_commit(mplx_poly3 *p);
+/* env_poly_map<3>::get_succ for K states (13 doubles each) in worlds world_of[k]; out: K x n_u records, [k * n_u + i] for input i */
+int mplx_poly3_get_succ_batch(mplx_poly3 *p, int32_t K, const int32_t *world_of, const double *states, mplx_poly3_succ *out);
+int mplx_poly3_set_capacity(mplx_poly3 *p, int32_t n_slots, uint64_t total_nodes, uint64_t total_edges, uint64_t total_open_log);
+/* PlannerBase::plan for n queries in ONE launch: query k in world world_of[k], starts / goals 13 doubles each; as mplx_poly_plan_batch */
+int mplx_poly3_plan_batch(mplx_poly3 *p, int32_t n, const int32_t *world_of, const double *starts, const double *goals, double eps, double tol_pos,
+                          double tol_vel, int32_t max_expand, int32_t heur_ignore_dynamics, mplx_result *out);
+/* trajectory of query q of the last batch: actions[traj_len], node_ids[traj_len + 1], states (traj_len + 1) x 13; NULLs allowed */
+int mplx_poly3_result_traj(mplx_poly3 *p, int32_t q, int32_t *actions, int32_t *node_ids, double *states);
+/* the state space of query q of the last batch (getCloseSet / getOpenSet): n_nodes states in id order, g, closed / opened flags */
+int mplx_poly3_result_nodes(mplx_poly3 *p, int32_t q, uint64_t cap, mplx_waypoint *states, double *g, int32_t *closed, int32_t *opened);
+int mplx_poly3_set_record(mplx_poly3 *p, uint32_t cap_per_query);
+int mplx_poly3_result_expanded(mplx_poly3 *p, int32_t q, uint32_t cap, int32_t *ids, uint32_t *n);
+int mplx_poly3_set_deadline(mplx_poly3 *p, double seconds); /* launch guard of the search (mplx_set_deadline) */
+int mplx_poly3_last_kernel_ms(const mplx_poly3 *p, float *ms);
+
 /* ---- after the search: refinement and sampling (host arithmetic, no context, no device) ----
  * TrajSolver3D(control).setWaypoints(wps).setDts(dts).solve(), map_planner_node.cpp:217-227: minimum-derivative
  * piecewise polynomial through n_wp waypoints (control kind VEL / ACC / JRK: minimum velocity / acceleration / jerk);

@@ -81,11 +81,19 @@ EXPORTS = [
     "mplx_cloud_create", "mplx_cloud_destroy", "mplx_cloud_last_error", "mplx_cloud_config", "mplx_cloud_set_map", "mplx_cloud_get_succ_batch",
     "mplx_cloud_last_point_tests", "mplx_cloud_set_capacity", "mplx_cloud_plan_batch", "mplx_cloud_result_traj", "mplx_cloud_result_nodes",
     "mplx_cloud_set_record", "mplx_cloud_result_expanded", "mplx_cloud_set_deadline", "mplx_cloud_last_kernel_ms",
+    "mplx_poly3_create", "mplx_poly3_destroy", "mplx_poly3_last_error", "mplx_poly3_config", "mplx_poly3_begin", "mplx_poly3_set_world",
+    "mplx_poly3_add_static", "mplx_poly3_add_linear", "mplx_poly3_add_nonlinear", "mplx_poly3_commit", "mplx_poly3_get_succ_batch",
+    "mplx_poly3_set_capacity", "mplx_poly3_plan_batch", "mplx_poly3_result_traj", "mplx_poly3_result_nodes", "mplx_poly3_set_record",
+    "mplx_poly3_result_expanded", "mplx_poly3_set_deadline", "mplx_poly3_last_kernel_ms",
 ]
 
 
 class PolySucc(C.Structure):
     _fields_ = [("state", C.c_double * 9), ("cost", C.c_double), ("action", C.c_int32), ("valid", C.c_int32)]
+
+
+class Poly3Succ(C.Structure):  # mplx_poly3_succ
+    _fields_ = [("state", C.c_double * 13), ("cost", C.c_double), ("action", C.c_int32), ("valid", C.c_int32)]
 
 _lib = None
 
@@ -280,5 +288,27 @@ def load():
     L.mplx_cloud_result_expanded.argtypes = [P, C.c_int32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     L.mplx_cloud_set_deadline.argtypes = [P, C.c_double]
     L.mplx_cloud_last_kernel_ms.argtypes = [P, C.POINTER(C.c_float)]
+    L.mplx_poly3_create.argtypes = [C.c_int, C.POINTER(P)]
+    L.mplx_poly3_destroy.argtypes = [P]
+    L.mplx_poly3_destroy.restype = None
+    L.mplx_poly3_last_error.argtypes = [P]
+    L.mplx_poly3_last_error.restype = C.c_char_p
+    L.mplx_poly3_config.argtypes = [P, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]
+    L.mplx_poly3_begin.argtypes = [P, C.c_int32]
+    L.mplx_poly3_set_world.argtypes = [P, C.c_int32, D2, D2, C.c_double]
+    L.mplx_poly3_add_static.argtypes = [P, C.c_int32, C.c_int32, C.c_void_p, D2]
+    L.mplx_poly3_add_linear.argtypes = [P, C.c_int32, C.c_int32, C.c_void_p, D2, D2, C.c_double]
+    L.mplx_poly3_add_nonlinear.argtypes = [P, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_int32, C.c_int32]
+    L.mplx_poly3_commit.argtypes = [P]
+    L.mplx_poly3_get_succ_batch.argtypes = [P, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(Poly3Succ)]
+    L.mplx_poly3_set_capacity.argtypes = [P, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.mplx_poly3_plan_batch.argtypes = [P, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                                        C.POINTER(Result)]
+    L.mplx_poly3_result_traj.argtypes = [P, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mplx_poly3_result_nodes.argtypes = [P, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mplx_poly3_set_record.argtypes = [P, C.c_uint32]
+    L.mplx_poly3_result_expanded.argtypes = [P, C.c_int32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.mplx_poly3_set_deadline.argtypes = [P, C.c_double]
+    L.mplx_poly3_last_kernel_ms.argtypes = [P, C.POINTER(C.c_float)]
     _lib = L
     return L

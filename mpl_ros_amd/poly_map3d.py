@@ -1,0 +1,189 @@
+"""Host mirror of the reference's 3-D moving-obstacle planner, PolyMapPlanner3D (poly_map_planner.h:107), over the C-ABI
+(mplx_poly3_*).  The 2-D interface (poly_map.py) one for one, with 3-D worlds: a `PolyWorld3D` is what one planner sees --
+setMap(ori, dim) with the six-face bounding box of poly_map_util.h:52-68, setStartTime, static / linear / nonlinear
+obstacles -- and a `PolyTeam3D` holds several worlds on the device so that many queries plan in one launch.  No compute
+happens here.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from ._capi import MplxError
+
+VEL, ACC, JRK, SNP = _capi.VEL, _capi.ACC, _capi.JRK, _capi.SNP
+
+
+def box(hx, hy=None, hz=None):
+    """Polyhedron3D of an axis-aligned box with half sizes (hx, hy, hz) around the origin: rows {px, py, pz, nx, ny, nz}"""
+    hy = hx if hy is None else hy
+    hz = hx if hz is None else hz
+    return np.array([[-hx, 0, 0, -1, -0.0, -0.0], [hx, 0, 0, 1, 0, 0], [0, -hy, 0, -0.0, -1, -0.0], [0, hy, 0, 0, 1, 0],
+                     [0, 0, -hz, -0.0, -0.0, -1], [0, 0, hz, 0, 0, 1]], dtype=np.float64)
+
+
+def control_lattice(u=1.0, num=1, u_z=None):
+    """U (n_u x 3): every axis from -u to u in steps of u / num, the loop variable accumulating the step as the nodes' for
+    loops do (dz from -u_z to u_z; u_z = 0: planar inputs)"""
+    def axis(m):
+        if m == 0:
+            return [0.0]
+        d, vals, x = m / num, [], -m
+        while x <= m:
+            vals.append(x)
+            x += d
+        return vals
+    zs = axis(u if u_z is None else u_z)
+    return np.array([(x, y, z) for x in axis(u) for y in axis(u) for z in zs], dtype=np.float64)
+
+
+class StaticObstacle3D:        # PolyhedronObstacle3D(poly, p)
+    def __init__(self, poly, p):
+        self.poly, self.p = np.ascontiguousarray(poly, dtype=np.float64).reshape(-1, 6), np.array(p, dtype=np.float64)
+
+
+class LinearObstacle3D:        # PolyhedronLinearObstacle3D(poly, p, v) + set_cov_v
+    def __init__(self, poly, p, v, cov_v=0.0):
+        self.poly, self.p, self.v, self.cov_v = np.ascontiguousarray(poly, dtype=np.float64).reshape(-1, 6), np.array(p, float), np.array(v, float), float(cov_v)
+
+
+class NonlinearObstacle3D:     # PolyhedronNonlinearObstacle3D(poly, traj, t) + disappear_front_/back_
+    def __init__(self, poly, segs, start_t, disappear_front=False, disappear_back=False):
+        """segs: rows {cx[6], cy[6], cz[6], T} -- the primitives of the obstacle's trajectory"""
+        self.poly = np.ascontiguousarray(poly, dtype=np.float64).reshape(-1, 6)
+        self.segs = np.ascontiguousarray(segs, dtype=np.float64).reshape(-1, 19)
+        self.start_t, self.disappear_front, self.disappear_back = float(start_t), bool(disappear_front), bool(disappear_back)
+
+
+class PolyWorld3D:
+    def __init__(self, ori, dim, start_t=0.0):
+        self.ori, self.dim, self.start_t = np.array(ori, float), np.array(dim, float), float(start_t)
+        self.static, self.linear, self.nonlinear = [], [], []
+
+
+def acc_segs(p0, v0, us, dt):
+    """Trajectory of ACC primitives from (p0, v0) under the inputs `us` (n x 3): rows {cx[6], cy[6], cz[6], T}"""
+    p, v = np.array(p0, float), np.array(v0, float)
+    rows = []
+    for u in us:
+        u = np.array(u, float)
+        rows.append(sum(([0, 0, 0, u[k], v[k], p[k]] for k in range(3)), []) + [dt])
+        p = u / 2 * dt * dt + v * dt + p
+        v = u * dt + v
+    return np.array(rows).reshape(-1, 19)
+
+
+def jrk_segs(p0, v0, a0, us, dt):
+    """Trajectory of JRK primitives from (p0, v0, a0) under the jerk inputs `us` (cubic segments): rows {cx[6], cy[6], cz[6], T}"""
+    p, v, a = np.array(p0, float), np.array(v0, float), np.array(a0, float)
+    rows = []
+    for u in us:
+        u = np.array(u, float)
+        rows.append(sum(([0, 0, u[k], a[k], v[k], p[k]] for k in range(3)), []) + [dt])
+        p = u / 6 * dt ** 3 + a / 2 * dt * dt + v * dt + p
+        v = u / 2 * dt * dt + a * dt + v
+        a = u * dt + a
+    return np.array(rows).reshape(-1, 19)
+
+
+class PolyTeam3D:
+    """The 3-D worlds of several planners on the device + the shared planner set-up (setVmax/setAmax/setDt/setU/setW)."""
+
+    def __init__(self, device=0):
+        self.lib = _capi.load()
+        self.h = C.c_void_p()
+        code = self.lib.mplx_poly3_create(device, C.byref(self.h))
+        if code != _capi.OK:
+            raise MplxError(self.lib.mplx_poly3_last_error(None).decode())
+        self.n_u = 0
+        self._results = []
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.lib.mplx_poly3_destroy(self.h)
+        except Exception:
+            pass
+
+    def check(self, code):
+        if code != _capi.OK:
+            raise MplxError(self.lib.mplx_poly3_last_error(self.h).decode())
+
+    def configure(self, control, U, dt, v_max=-1.0, a_max=-1.0, j_max=-1.0, w=10.0):
+        U = np.ascontiguousarray(U, dtype=np.float64).reshape(-1, 3)
+        self.n_u = U.shape[0]
+        self.check(self.lib.mplx_poly3_config(self.h, int(control), self.n_u, U.ctypes.data, float(dt), float(v_max), float(a_max), float(j_max), float(w)))
+
+    def set_worlds(self, worlds):
+        self.check(self.lib.mplx_poly3_begin(self.h, len(worlds)))
+        D3 = C.c_double * 3
+        for i, W in enumerate(worlds):
+            self.check(self.lib.mplx_poly3_set_world(self.h, i, D3(*W.ori), D3(*W.dim), W.start_t))
+            for o in W.static:
+                self.check(self.lib.mplx_poly3_add_static(self.h, i, len(o.poly), o.poly.ctypes.data, D3(*o.p)))
+            for o in W.linear:
+                self.check(self.lib.mplx_poly3_add_linear(self.h, i, len(o.poly), o.poly.ctypes.data, D3(*o.p), D3(*o.v), o.cov_v))
+            for o in W.nonlinear:
+                self.check(self.lib.mplx_poly3_add_nonlinear(self.h, i, len(o.poly), o.poly.ctypes.data, len(o.segs), o.segs.ctypes.data,
+                                                             o.start_t, int(o.disappear_front), int(o.disappear_back)))
+        self.check(self.lib.mplx_poly3_commit(self.h))
+
+    def get_succ_batch(self, world_of, states):
+        """env_poly_map<3>::get_succ for K states (K x 13: pos3 vel3 acc3 jrk3 t); returns K x n_u records."""
+        w = np.ascontiguousarray(world_of, dtype=np.int32)
+        s = np.ascontiguousarray(states, dtype=np.float64).reshape(-1, 13)
+        out = (_capi.Poly3Succ * (len(w) * self.n_u))()
+        self.check(self.lib.mplx_poly3_get_succ_batch(self.h, len(w), w.ctypes.data, s.ctypes.data, out))
+        return out
+
+    def set_capacity(self, n_slots, nodes, edges, open_log):
+        self.check(self.lib.mplx_poly3_set_capacity(self.h, int(n_slots), int(nodes), int(edges), int(open_log)))
+
+    def set_deadline(self, seconds):
+        self.check(self.lib.mplx_poly3_set_deadline(self.h, float(seconds)))
+
+    def set_record(self, cap):
+        self.check(self.lib.mplx_poly3_set_record(self.h, int(cap)))
+
+    def plan_batch(self, world_of, starts, goals, eps=1.0, tol_pos=0.5, tol_vel=-1.0, max_expand=-1, heur_ignore_dynamics=True):
+        """PlannerBase::plan for one query per entry, all in one launch; starts / goals: n x 13 (pos3 vel3 acc3 jrk3 t)."""
+        w = np.ascontiguousarray(world_of, dtype=np.int32)
+        s = np.ascontiguousarray(starts, dtype=np.float64).reshape(-1, 13)
+        g = np.ascontiguousarray(goals, dtype=np.float64).reshape(-1, 13)
+        R = (_capi.Result * len(w))()
+        self.check(self.lib.mplx_poly3_plan_batch(self.h, len(w), w.ctypes.data, s.ctypes.data, g.ctypes.data, float(eps), float(tol_pos), float(tol_vel),
+                                                  int(max_expand), int(bool(heur_ignore_dynamics)), R))
+        self._results = [R[i] for i in range(len(w))]
+        return self._results
+
+    def traj(self, q):
+        """(actions, node ids, states (n + 1) x 13) of query q of the last batch"""
+        r = self._results[q]
+        n = r.traj_len if r.status == _capi.PLAN_OK else 0
+        act = np.zeros(max(n, 1), dtype=np.int32); ids = np.zeros(n + 1, dtype=np.int32); st = np.zeros((n + 1, 13))
+        if n:
+            self.check(self.lib.mplx_poly3_result_traj(self.h, q, act.ctypes.data, ids.ctypes.data, st.ctypes.data))
+        return act[:n], ids[:n + 1] if n else ids[:0], st[:n + 1] if n else st[:0]
+
+    def nodes(self, q):
+        """The state space of query q (getCloseSet / getOpenSet): states (n x 13), g, closed, opened"""
+        n = int(self._results[q].n_nodes)
+        wps = (_capi.Waypoint * max(n, 1))()
+        g = np.zeros(max(n, 1)); closed = np.zeros(max(n, 1), dtype=np.int32); opened = closed.copy()
+        self.check(self.lib.mplx_poly3_result_nodes(self.h, q, max(n, 1), wps, g.ctypes.data, closed.ctypes.data, opened.ctypes.data))
+        st = np.zeros((n, 13))
+        for i in range(n):
+            st[i, 0:3], st[i, 3:6], st[i, 6:9], st[i, 9:12], st[i, 12] = wps[i].pos[:], wps[i].vel[:], wps[i].acc[:], wps[i].jrk[:], wps[i].t
+        return st, g[:n], closed[:n], opened[:n]
+
+    def expanded_ids(self, q):
+        cap = int(self._results[q].n_expanded)
+        ids = np.zeros(max(cap, 1), dtype=np.int32)
+        n = C.c_uint32()
+        self.check(self.lib.mplx_poly3_result_expanded(self.h, q, cap, ids.ctypes.data, C.byref(n)))
+        return ids[:n.value]
+
+    def last_kernel_ms(self):
+        ms = C.c_float()
+        self.check(self.lib.mplx_poly3_last_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
