@@ -2,7 +2,9 @@
 //
 //  * expand_kernel   : env_map::get_succ for K nodes, one workgroup per node (unit-test entry).
 //  * astar_kernel    : GraphSearch::Astar resident on the device, one workgroup per in-flight query,
-//                      queries pulled from a device counter (persistent workgroups).
+//                      queries pulled from a device counter (persistent workgroups).  Its per-query steps (reset,
+//                      admission, start node, duplicate probe, termination, recoverTraj) are those of
+//                      mplx_search_steps.h, shared with the other A* kernels.
 //
 // Work decomposition of one expansion (get_succ call sites: env_poly_map.h:45-69, env_cloud.h:50-70):
 //   phase 1  lane = control input   : build primitive, end state, key, validate, sample count
@@ -1497,6 +1499,12 @@ __device__ __forceinline__ bool pop_min(const QView<BLOCK, CONTROL, SM> &Q, int 
   }
 }
 
+}  // namespace mplx
+
+#include "mplx_search_steps.h"  // the per-query steps shared by the A* kernels (needs QView, open_push, pop_min)
+
+namespace mplx {
+
 // ------------------------------------------------------------------ astar_kernel
 // YAW: yaw-carrying states (use_yaw lattices, map_planner_node.cpp:119-139,165): one more key integer, one more state
 // double, validate_yaw; edge costs and the heuristic are those of the yaw-less search [UNVERIFIED upstream: Jyaw is a
@@ -1507,9 +1515,9 @@ __global__ __launch_bounds__(BLOCK) void astar_kernel(SearchParams P) {
   using V = QView<BLOCK, CONTROL>;
   const int tid = threadIdx.x;
   const V Q{P, S, P.bkt_head + (size_t)blockIdx.x * 2 * NB * NSUB};
-  constexpr int nk = key_len_c(CONTROL), ns = key_len_c(CONTROL), NKY = nk + (YAW ? 1 : 0), EX = YAW ? 1 : 0;
+  constexpr int nk = key_len_c(CONTROL), NKY = nk + (YAW ? 1 : 0), EX = YAW ? 1 : 0;  // key integers / extra state doubles (the yaw) of a record
   // is_goal with the yaw tolerance of a yaw-carrying search
-  auto goal_reached = [&](const State &s, double yaw, const QueryIn &in) {
+  auto goal_reached = [&](const State &s, double yaw) {
     bool g = is_goal_state(s, S.hp.goal, S.hp.goal_control & 15, P.tol_pos, P.tol_vel, P.tol_acc);  // (the LDS copy of the goal)
     if (YAW && g && P.tol_yaw >= 0) g = fabs(yaw - S.hp.goal_yaw) <= P.tol_yaw;
     return g;
@@ -1530,87 +1538,17 @@ __global__ __launch_bounds__(BLOCK) void astar_kernel(SearchParams P) {
     const int q = P.order[qi];
     const QueryIn &in = P.queries[q];
     const unsigned long long t_begin = wall_clock64();
-    // ---- reset the workgroup's OPEN structure
-    for (int i = tid; i < 2 * NB; i += BLOCK) S.cnt[0][i] = 0;
-    if (tid == 0) {
-      S.n_near = 0; S.n_nodes = 0; S.n_edges = 0; S.n_log = 0;
-      S.reserve = (uint32_t)P.n_u;
-      S.node_chunks = S.edge_chunks = S.open_chunks = 0;
-      S.cur1 = 0; S.cur0 = 0; S.lo1 = 0.0; S.ts_f = INFINITY; S.ts_g = INFINITY; S.ts_id = 0xFFFFFFFFu;
-      S.status = -1;
-      for (int i = 0; i < 10; i++) S.cyc[i] = 0;
-      S.c_expanded = S.c_closed = S.c_prims = S.c_succ = S.c_succ_finite = S.c_reads = 0;
-      S.c_push = S.c_reopen = S.c_refill = S.c_evict = 0;
-      S.c_hash = 0;
-      S.hp.w = P.w; S.hp.v_max = P.v_max; S.hp.heur_ignore_dynamics = P.heur_ignore_dynamics;
-      S.hp.goal_control = in.goal_control;
-      S.hp.goal = in.goal;
-      S.hp.goal_nkey = state_key(in.goal_control, in.goal, S.hp.goal_key);
-      S.hp.goal_yaw = in.goal_yaw;
-      S.hp.goal_yaw_key = (int32_t)round(in.goal_yaw / KEY_RES_YAW);
-      // PlannerBase::plan: start must be free; Astar: already at goal -> cost 0
-      int32_t c[3];
-      bool free_ = true;
-      for (int ax = 0; ax < 3; ax++) {
-        c[ax] = float_to_cell(in.start.p[ax], P.map.origin[ax], P.map.res);
-        if (c[ax] < 0 || c[ax] >= P.map.dim[ax]) free_ = false;
-      }
-      if (free_) free_ = P.map.data[(size_t)c[0] + (size_t)P.map.dim[0] * c[1] + (size_t)P.map.dim[0] * P.map.dim[1] * c[2]] == 0;
-      double cost0 = INFINITY;
-      if (!free_)
-        S.status = 2;
-      else if (in.start_t >= P.t_max || goal_reached(in.start, in.start_yaw, in)) {
-        S.status = 0;
-        cost0 = 0.0;
-      }
-      S.tmp_d0 = cost0;
-      if (S.status < 0) {
-        bool ok = ensure_chunks(S.node_tbl, S.node_chunks, 1, NODE_CH_LOG, MAX_NODE_CH, P.chunk_next + 0, P.node_chunks) &&
-                  ensure_chunks(S.open_tbl, S.open_chunks, 1, OPEN_CH_LOG, MAX_OPEN_CH, P.chunk_next + 2, P.open_chunks);
-        if (!ok) S.status = 4;
-      }
-    }
+    query_reset(Q, in, (uint32_t)P.n_u, tid);
+    if (tid == 0) query_admit(Q, in, voxel_start_free(P, in), goal_reached(in.start, in.start_yaw));
     __syncthreads();
     uint32_t goal_id = NIL;
     if (S.status < 0) {
-      // ---- start node (id 0)
-      if (tid == 0) {
-        int32_t key[MAX_KEY + 1];
-        state_key_c<CONTROL>(in.start, key);
-        const int32_t ykey = (int32_t)round(in.start_yaw / KEY_RES_YAW);
-        if (YAW) key[nk] = ykey;
-        char *rec = Q.node(0);
-        for (int i = 0; i < NKY; i++) V::key(rec)[i] = key[i];
-        const double *src = (const double *)&in.start;
-        for (int i = 0; i < ns; i++) V::state(rec)[i] = src[i];
-        if (YAW) V::state(rec)[ns] = in.start_yaw;
-        V::state(rec)[ns + EX] = in.start_t;
-        double h = 0.0;
-        if (P.eps != 0.0) h = (YAW && ykey != S.hp.goal_yaw_key) ? cal_heur(S.hp, CONTROL, in.start) : get_heur(S.hp, CONTROL, in.start, key, nk);
-        V::h(rec) = h;
-        V::g(rec) = 0.0;
-        V::flags(rec) = FLAG_OPENED;
-        V::pred(rec) = NIL;
-        const unsigned long long h64 = key_hash64(key, NKY);
-        const unsigned long long tagq = tbl_tagq(h64, (uint32_t)q, P.tbl_epoch);
-        size_t pos = (size_t)(h64 ^ ((unsigned long long)(uint32_t)q * 0x9E3779B97F4A7C15ull)) & (size_t)P.table_mask;
-        for (unsigned long long steps = 0;; steps++) {  // shared table: the home slot may belong to another query
-          const unsigned long long seen = ld_u64(&P.table[pos]);  // (a slot of another epoch is empty: claimed against the value seen)
-          if (tbl_empty(seen, P.tbl_epoch) && atomicCAS(&P.table[pos], seen, tagq | 0ull) == seen) break;
-          if (steps > P.table_mask) { S.status = 5; break; }  // (the table is full: never with the host's sizing)
-          pos = (pos + 1) & (size_t)P.table_mask;
-        }
-        S.n_nodes = 1;
-        S.f_base = 0.0 + P.eps * h;
-        S.lo1 = S.f_base;
-        S.n_log = 1;
-        S.c_push = 1;
-      }
-      __syncthreads();
-      if (tid == 0) open_push(Q, 0u, S.f_base, 0.0, 0u);
-      __syncthreads();
+      const int32_t ykey = (int32_t)round(in.start_yaw / KEY_RES_YAW);
+      const bool started = query_start<NKY, EX>(Q, in, q, tid, ykey, in.start_yaw, [&](const int32_t *key) {
+        return (YAW && ykey != S.hp.goal_yaw_key) ? cal_heur(S.hp, CONTROL, in.start) : get_heur(S.hp, CONTROL, in.start, key, nk);
+      });
       // ---- main loop
-      for (;;) {
+      if (started) for (;;) {
         while (S.n_near + S.reserve > (uint32_t)NC) {  // Smem<BLOCK>::NCAP == NC here
           MPLX_TIC(te);
           evict_half(Q, tid);
@@ -1651,11 +1589,8 @@ __global__ __launch_bounds__(BLOCK) void astar_kernel(SearchParams P) {
             S.c_reads += treads;
           }
         }
-        // duplicate keys inside this expansion? (LDS set over the 64-bit key hashes)
+        // duplicate keys inside this expansion?
         unsigned long long h64 = 0;
-        S.dupset[tid] = 0;
-        S.dupset[tid + BLOCK] = 0;
-        __syncthreads();
         if (act) {
           if constexpr (YAW) {
             int32_t kk[MAX_KEY + 1];
@@ -1666,16 +1601,8 @@ __global__ __launch_bounds__(BLOCK) void astar_kernel(SearchParams P) {
           } else {
             h64 = key_hash64(L.key, nk);
           }
-          const unsigned long long hv = h64 | 1ull;
-          uint32_t sl = (uint32_t)(h64 >> 7) & (2 * BLOCK - 1);
-          for (;;) {
-            unsigned long long old = atomicCAS(&S.dupset[sl], 0ull, hv);
-            if (old == 0ull) break;
-            if (old == hv) { S.flag = 1; break; }
-            sl = (sl + 1) & (2 * BLOCK - 1);
-          }
         }
-        __syncthreads();
+        dup_probe<BLOCK>(S, act, h64, tid);
         // edge cost: J + w dt of the control input, plus the potential term when a potential map exists
         const double lane_cost = act ? (P.map.aux ? S.ucost_lds[tid] + P.pot_weight * (double)L.pot : S.ucost_lds[tid]) : 0.0;
         const uint32_t action_tag = (uint32_t)tid | (L.pot << EDGE_POT_SHIFT);
@@ -1688,97 +1615,19 @@ __global__ __launch_bounds__(BLOCK) void astar_kernel(SearchParams P) {
         __syncthreads();
         MPLX_TOC(S, 2, tc);
         if (S.status >= 0) break;  // pool full
-        // ---- termination tests, in the order of the reference loop: goal, max_expand (empty OPEN: next pop)
-        if (tid == 0) {
-          State s;
-          for (int i = 0; i < 12; i++) ((double *)&s)[i] = S.cur[0][i];
-          if (S.cur[0][12] >= P.t_max || goal_reached(s, S.cur_yaw[0], in))
-            S.status = 0;
-          else if (P.max_expand > 0 && S.c_expanded >= (unsigned long long)P.max_expand)
-            S.status = 3;
-          else if ((S.c_expanded & 63ull) == 0ull) {  // launch guard: heartbeat + abort word, every 64th expansion
-            guard_mark(P, GUARD_BATCH, (uint32_t)q, S.c_expanded, (unsigned long long)S.n_nodes);
-            if (guard_abort(P)) S.status = PLAN_ABORTED;
-          }
-        }
-        __syncthreads();
-        if (S.status >= 0) break;
+        if (search_ended(Q, q, tid, [&](const State &s) { return goal_reached(s, S.cur_yaw[0]); })) break;
       }
       goal_id = S.cur_id;
       clear_buckets(Q, tid);
     }
     __syncthreads();
     // ---- recoverTraj + results (thread 0)
-    if (tid == 0) {
-      QueryOut &o = P.out[q];
-      int32_t *tn = P.traj_nodes + (size_t)q * (MAX_TRAJ + 1);
-      int32_t *ta = P.traj_actions + (size_t)q * MAX_TRAJ;
-      double *ts = P.traj_states + (size_t)q * (MAX_TRAJ + 1) * 13;
-      int status = S.status;
-      double cost = INFINITY;
-      int len = 0;
-      if (status == 0 && goal_id == NIL) {
-        cost = S.tmp_d0;  // start already satisfied the goal
-      } else if (status == 0) {
-        // walk predecessor records: minimise g(pred) + edge cost, ties -> larger g(pred), then the
-        // oldest record.  Written goal -> start; the host reverses.
-        uint32_t node = goal_id;
-        tn[0] = (int32_t)node;
-        bool ok = true, too_long = false;
-        while (V::pred(Q.node(node)) != NIL) {
-          uint32_t best = NIL;
-          double min_rhs = INFINITY, min_g = INFINITY;
-          uint32_t hops = 0;
-          for (uint32_t e = V::pred(Q.node(node)); e != NIL && hops <= S.n_edges; e = Q.edge(e)->next, hops++) {
-            const EdgeRec er = *Q.edge(e);
-            double gp = V::g(Q.node(er.parent));
-            const double ec = P.map.aux ? P.ucost[er.action & EDGE_ACTION_MASK] + P.pot_weight * (double)(er.action >> EDGE_POT_SHIFT) : P.ucost[er.action & EDGE_ACTION_MASK];
-            double rhs = gp + ec;
-            if (rhs < min_rhs || (rhs == min_rhs && gp >= min_g)) { min_rhs = rhs; min_g = gp; best = e; }
-          }
-          if (best == NIL) { ok = false; break; }
-          if (len >= MAX_TRAJ) { too_long = true; break; }
-          ta[len] = (int32_t)(Q.edge(best)->action & EDGE_ACTION_MASK);
-          node = Q.edge(best)->parent;
-          len++;
-          tn[len] = (int32_t)node;
-          if (node == 0u) break;
-        }
-        if (too_long) {  // goal reached and cost known; the path does not fit the device-side buffer
-          cost = V::g(Q.node(goal_id));
-          status = 6;    // MPLX_PLAN_TRAJ_TOO_LONG
-          len = 0;
-        } else if (ok) {
-          cost = V::g(Q.node(goal_id));
-          for (int i = 0; i <= len; i++) {
-            const double *st = V::state(Q.node((uint32_t)tn[i]));
-            for (int k = 0; k < 12; k++) ts[i * 13 + k] = k < ns ? st[k] : 0.0;
-            ts[i * 13 + 12] = st[ns + EX];
-            if (YAW && P.traj_yaw) P.traj_yaw[(size_t)q * (MAX_TRAJ + 1) + i] = st[ns];
-          }
-        } else {
-          status = 1;
-          len = 0;
-        }
-      }
-      o.status = status;
-      o.traj_len = len;
-      o.cost = cost;
-      o.n_expanded = S.c_expanded; o.n_closed = S.c_closed; o.n_nodes = S.n_nodes; o.n_edges = S.n_edges;
-      o.n_primitives = S.c_prims; o.n_succ = S.c_succ; o.n_succ_finite = S.c_succ_finite; o.voxel_reads = S.c_reads;
-      o.n_push = S.c_push; o.n_reopen = S.c_reopen; o.n_refill = S.c_refill; o.n_evict = S.c_evict;
-      o.expand_hash = S.c_hash;
-      o.n_recorded = (uint32_t)(S.c_expanded < P.cap_rec ? S.c_expanded : P.cap_rec);
-      o.slot = blockIdx.x;
-      o.spec[0] = o.spec[1] = o.spec[2] = o.spec[3] = 0;  // (one node per iteration: nothing speculative)
-      o.t_begin = t_begin;
-      o.t_end = wall_clock64();
-      for (int i = 0; i < 10; i++) o.cyc[i] = S.cyc[i];
-    }
-    for (uint32_t i = tid; i < (uint32_t)MAX_NODE_CH; i += BLOCK)
-      P.node_tables[(size_t)q * MAX_NODE_CH + i] = i < S.node_chunks ? S.node_tbl[i] : NIL;
-    for (uint32_t i = tid; i < (uint32_t)MAX_EDGE_CH; i += BLOCK)
-      P.edge_tables[(size_t)q * MAX_EDGE_CH + i] = i < S.edge_chunks ? S.edge_tbl[i] : NIL;
+    // edge cost: J + w dt of the control input, plus the potential term when a potential map exists
+    if (tid == 0)
+      query_report<EX>(Q, q, goal_id, [&](uint32_t, uint32_t action) {
+        return P.map.aux ? P.ucost[action & EDGE_ACTION_MASK] + P.pot_weight * (double)(action >> EDGE_POT_SHIFT) : P.ucost[action & EDGE_ACTION_MASK];
+      }, SpecCounts{}, t_begin);
+    publish_chunk_tables(Q, q, tid);
     __syncthreads();
   }
 }

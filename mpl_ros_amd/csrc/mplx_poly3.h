@@ -14,8 +14,8 @@
 // host evaluation.  Compiled -ffp-contract=off like the rest.
 //
 // Shared unchanged with the 2-D environment: pp_p / pp_v / pp_a / pp_j / pp_J, solve_le2 / solve_any6 / solve_poly<GEN>,
-// poly_max_abs (mplx_poly_dev.h); the search machinery of astar_kernel (mplx_kernels.h: Smem, QView, pools, table,
-// heuristics, commit_parallel, recoverTraj).  GEN = false: hyperplane equations of degree <= 2 (ACC primitives among
+// poly_max_abs (mplx_poly_dev.h); the search machinery of mplx_kernels.h (Smem, QView, pools, table, heuristics,
+// commit_parallel) and the per-query steps of mplx_search_steps.h.  GEN = false: hyperplane equations of degree <= 2 (ACC primitives among
 // static / linear obstacles and obstacles on VEL / ACC trajectories); a higher degree is reported, never approximated.
 // GEN = true: any degree up to five through solve_any6 (JRK primitives, obstacle trajectories with cubic or higher segments).
 //
@@ -355,7 +355,7 @@ __global__ __launch_bounds__(BLOCK) void poly3_get_succ_kernel(Poly3Dev D, int K
   }
 }
 
-// ---- GraphSearch::Astar over env_poly_map<3>: astar_poly_kernel's leader loop (mplx_poly_search.h) with the 3-D get_succ.
+// ---- GraphSearch::Astar over env_poly_map<3>: the per-query steps of mplx_search_steps.h around the 3-D get_succ.
 // Time-keyed states (key: the state's integers + round(t / 0.1), env_poly_map.h:63-64), the edge cost travels with the lane
 // and recoverTraj recomputes it from the parent state; PlannerBase::plan's start test is isInside(start.pos).
 template <int BLOCK, int CONTROL, bool GEN>
@@ -383,75 +383,18 @@ __global__ __launch_bounds__(BLOCK) void astar_poly3_kernel(SearchParams P, Poly
     const QueryIn &in = P.queries[q];
     const Poly3World &W = D.worlds[D.world_of[q]];
     const unsigned long long t_begin = wall_clock64();
-    for (int i = tid; i < 2 * NB; i += BLOCK) S.cnt[0][i] = 0;
+    query_reset(Q, in, (uint32_t)P.n_u, tid);
     if (tid == 0) {
-      S.n_near = 0; S.n_nodes = 0; S.n_edges = 0; S.n_log = 0;
-      S.reserve = (uint32_t)P.n_u;
-      S.node_chunks = S.edge_chunks = S.open_chunks = 0;
-      S.cur1 = 0; S.cur0 = 0; S.lo1 = 0.0; S.ts_f = INFINITY; S.ts_g = INFINITY; S.ts_id = 0xFFFFFFFFu;
-      S.status = -1;
-      for (int i = 0; i < 10; i++) S.cyc[i] = 0;
-      S.c_expanded = S.c_closed = S.c_prims = S.c_succ = S.c_succ_finite = S.c_reads = 0;
-      S.c_push = S.c_reopen = S.c_refill = S.c_evict = 0;
-      S.c_hash = 0;
       punsupported = 0;
-      S.hp.w = P.w; S.hp.v_max = P.v_max; S.hp.heur_ignore_dynamics = P.heur_ignore_dynamics;
-      S.hp.goal_control = in.goal_control;
-      S.hp.goal = in.goal;
-      S.hp.goal_nkey = state_key(in.goal_control, in.goal, S.hp.goal_key);
-      S.hp.goal_yaw = 0.0;
-      S.hp.goal_yaw_key = 0;
-      double cost0 = INFINITY;
-      if (!p3_inside(W.bbox, 6, in.start.p[0], in.start.p[1], in.start.p[2]))
-        S.status = 2;  // ENV_->is_free(start.pos) failed
-      else if (in.start_t >= P.t_max || is_goal_state(in.start, in.goal, in.goal_control, P.tol_pos, P.tol_vel, P.tol_acc)) {
-        S.status = 0;
-        cost0 = 0.0;
-      }
-      S.tmp_d0 = cost0;
-      if (S.status < 0) {
-        bool ok = ensure_chunks(S.node_tbl, S.node_chunks, 1, NODE_CH_LOG, MAX_NODE_CH, P.chunk_next + 0, P.node_chunks) &&
-                  ensure_chunks(S.open_tbl, S.open_chunks, 1, OPEN_CH_LOG, MAX_OPEN_CH, P.chunk_next + 2, P.open_chunks);
-        if (!ok) S.status = 4;
-      }
+      // ENV_->is_free(start.pos): inside the bounding box
+      query_admit(Q, in, p3_inside(W.bbox, 6, in.start.p[0], in.start.p[1], in.start.p[2]), is_goal_state(in.start, in.goal, in.goal_control, P.tol_pos, P.tol_vel, P.tol_acc));
     }
     __syncthreads();
     uint32_t goal_id = NIL;
     if (S.status < 0) {
-      if (tid == 0) {  // start node (id 0); its key carries the start time
-        int32_t key[MAX_KEY];
-        state_key_c<CONTROL>(in.start, key);
-        key[ns] = (int32_t)round(in.start_t / 0.1);
-        char *rec = Q.node(0);
-        for (int i = 0; i < NK; i++) V::key(rec)[i] = key[i];
-        const double *src = (const double *)&in.start;
-        for (int i = 0; i < ns; i++) V::state(rec)[i] = src[i];
-        V::state(rec)[ns] = in.start_t;
-        const double h = P.eps == 0.0 ? 0.0 : get_heur(S.hp, CONTROL, in.start, key, NK);
-        V::h(rec) = h;
-        V::g(rec) = 0.0;
-        V::flags(rec) = FLAG_OPENED;
-        V::pred(rec) = NIL;
-        const unsigned long long h64 = key_hash64(key, NK);
-        const unsigned long long tagq = tbl_tagq(h64, (uint32_t)q, P.tbl_epoch);
-        size_t pos = (size_t)(h64 ^ ((unsigned long long)(uint32_t)q * 0x9E3779B97F4A7C15ull)) & (size_t)P.table_mask;
-        for (unsigned long long steps = 0;; steps++) {
-          const unsigned long long seen = ld_u64(&P.table[pos]);
-          if (tbl_empty(seen, P.tbl_epoch) && atomicCAS(&P.table[pos], seen, tagq | 0ull) == seen) break;
-          if (steps > P.table_mask) { S.status = 5; break; }
-          pos = (pos + 1) & (size_t)P.table_mask;
-        }
-        S.n_nodes = 1;
-        S.f_base = 0.0 + P.eps * h;
-        S.lo1 = S.f_base;
-        S.n_log = 1;
-        S.c_push = 1;
-      }
-      __syncthreads();
-      if (tid == 0 && S.status < 0) open_push(Q, 0u, S.f_base, 0.0, 0u);
-      __syncthreads();
-      for (;;) {
-        if (S.status >= 0) break;
+      // (the start's key carries the start time)
+      const bool started = query_start<NK, 0>(Q, in, q, tid, (int32_t)round(in.start_t / 0.1), 0.0, [&](const int32_t *key) { return get_heur(S.hp, CONTROL, in.start, key, NK); });
+      if (started) for (;;) {
         while (S.n_near + S.reserve > (uint32_t)NC) {
           evict_half(Q, tid);
           __syncthreads();
@@ -512,23 +455,9 @@ __global__ __launch_bounds__(BLOCK) void astar_poly3_kernel(SearchParams P, Poly
             if (punsupported) S.status = 5;
           }
         }
-        S.dupset[tid] = 0;
-        S.dupset[tid + BLOCK] = 0;
-        __syncthreads();
+        const unsigned long long h64 = act ? key_hash64(L.key, NK) : 0ull;
+        dup_probe<BLOCK>(S, act, h64, tid);  // (its first barrier publishes the status)
         if (S.status >= 0) break;
-        unsigned long long h64 = 0;
-        if (act) {
-          h64 = key_hash64(L.key, NK);
-          const unsigned long long hv = h64 | 1ull;
-          uint32_t sl = (uint32_t)(h64 >> 7) & (2 * BLOCK - 1);
-          for (;;) {
-            unsigned long long old = atomicCAS(&S.dupset[sl], 0ull, hv);
-            if (old == 0ull) break;
-            if (old == hv) { S.flag = 1; break; }
-            sl = (sl + 1) & (2 * BLOCK - 1);
-          }
-        }
-        __syncthreads();
         if (!S.flag) {
           commit_parallel<BLOCK, CONTROL, Smem<BLOCK>, NK, false>(Q, tid, q, act, L, h64, lane_cost, (uint32_t)tid);
         } else {
@@ -537,98 +466,21 @@ __global__ __launch_bounds__(BLOCK) void astar_poly3_kernel(SearchParams P, Poly
         }
         __syncthreads();
         if (S.status >= 0) break;  // pool full
-        if (tid == 0) {
-          State s;
-          for (int i = 0; i < 12; i++) ((double *)&s)[i] = S.cur[0][i];
-          if (S.cur[0][12] >= P.t_max || is_goal_state(s, S.hp.goal, S.hp.goal_control, P.tol_pos, P.tol_vel, P.tol_acc))
-            S.status = 0;
-          else if (P.max_expand > 0 && S.c_expanded >= (unsigned long long)P.max_expand)
-            S.status = 3;
-          else if ((S.c_expanded & 63ull) == 0ull) {  // launch guard: heartbeat + abort word, every 64th expansion
-            guard_mark(P, GUARD_BATCH, (uint32_t)q, S.c_expanded, (unsigned long long)S.n_nodes);
-            if (guard_abort(P)) S.status = PLAN_ABORTED;
-          }
-        }
-        __syncthreads();
-        if (S.status >= 0) break;
+        if (search_ended(Q, q, tid, [&](const State &s) { return is_goal_state(s, S.hp.goal, S.hp.goal_control, P.tol_pos, P.tol_vel, P.tol_acc); })) break;
       }
       goal_id = S.cur_id;
       clear_buckets(Q, tid);
     }
     __syncthreads();
-    if (tid == 0) {  // recoverTraj + results
-      QueryOut &o = P.out[q];
-      int32_t *tn = P.traj_nodes + (size_t)q * (MAX_TRAJ + 1);
-      int32_t *ta = P.traj_actions + (size_t)q * MAX_TRAJ;
-      double *ts = P.traj_states + (size_t)q * (MAX_TRAJ + 1) * 13;
-      int status = S.status;
-      double cost = INFINITY;
-      int len = 0;
-      auto edge_cost = [&](uint32_t parent, uint32_t action) {  // calculate_intrinsic_cost of Primitive(parent, U[action], dt)
+    if (tid == 0)  // recoverTraj + results
+      query_report<0>(Q, q, goal_id, [&](uint32_t parent, uint32_t action) {  // calculate_intrinsic_cost of Primitive(parent, U[action], dt)
         const double *st = V::state(Q.node(parent));
         const double zero3[3] = {0.0, 0.0, 0.0};
         double c[3][6];
-        p3_prim_build(CONTROL, st, st + 3, CONTROL == CTRL_JRK ? st + 6 : zero3, zero3, D.U + 3 * action, c);
+        p3_prim_build(CONTROL, st, st + 3, CONTROL == CTRL_JRK ? st + 6 : zero3, zero3, D.U + 3 * (action & EDGE_ACTION_MASK), c);
         return p3_intrinsic_cost(CONTROL, c, P.dt, P.w, P.dt);
-      };
-      if (status == 0 && goal_id == NIL) {
-        cost = S.tmp_d0;
-      } else if (status == 0) {
-        uint32_t node = goal_id;
-        tn[0] = (int32_t)node;
-        bool ok = true, too_long = false;
-        while (V::pred(Q.node(node)) != NIL) {
-          uint32_t best = NIL;
-          double min_rhs = INFINITY, min_g = INFINITY;
-          uint32_t hops = 0;
-          for (uint32_t e = V::pred(Q.node(node)); e != NIL && hops <= S.n_edges; e = Q.edge(e)->next, hops++) {
-            const EdgeRec er = *Q.edge(e);
-            const double gp = V::g(Q.node(er.parent));
-            const double rhs = gp + edge_cost(er.parent, er.action & EDGE_ACTION_MASK);
-            if (rhs < min_rhs || (rhs == min_rhs && gp >= min_g)) { min_rhs = rhs; min_g = gp; best = e; }
-          }
-          if (best == NIL) { ok = false; break; }
-          if (len >= MAX_TRAJ) { too_long = true; break; }
-          ta[len] = (int32_t)(Q.edge(best)->action & EDGE_ACTION_MASK);
-          node = Q.edge(best)->parent;
-          len++;
-          tn[len] = (int32_t)node;
-          if (node == 0u) break;
-        }
-        if (too_long) {
-          cost = V::g(Q.node(goal_id));
-          status = 6;
-          len = 0;
-        } else if (ok) {
-          cost = V::g(Q.node(goal_id));
-          for (int i = 0; i <= len; i++) {
-            const double *st = V::state(Q.node((uint32_t)tn[i]));
-            for (int k = 0; k < 12; k++) ts[i * 13 + k] = k < ns ? st[k] : 0.0;
-            ts[i * 13 + 12] = st[ns];
-          }
-        } else {
-          status = 1;
-          len = 0;
-        }
-      }
-      o.status = status;
-      o.traj_len = len;
-      o.cost = cost;
-      o.n_expanded = S.c_expanded; o.n_closed = S.c_closed; o.n_nodes = S.n_nodes; o.n_edges = S.n_edges;
-      o.n_primitives = S.c_prims; o.n_succ = S.c_succ; o.n_succ_finite = S.c_succ_finite; o.voxel_reads = 0;
-      o.n_push = S.c_push; o.n_reopen = S.c_reopen; o.n_refill = S.c_refill; o.n_evict = S.c_evict;
-      o.expand_hash = S.c_hash;
-      o.n_recorded = (uint32_t)(S.c_expanded < P.cap_rec ? S.c_expanded : P.cap_rec);
-      o.slot = blockIdx.x;
-      o.spec[0] = o.spec[1] = o.spec[2] = o.spec[3] = 0;
-      o.t_begin = t_begin;
-      o.t_end = wall_clock64();
-      for (int i = 0; i < 10; i++) o.cyc[i] = S.cyc[i];
-    }
-    for (uint32_t i = tid; i < (uint32_t)MAX_NODE_CH; i += BLOCK)
-      P.node_tables[(size_t)q * MAX_NODE_CH + i] = i < S.node_chunks ? S.node_tbl[i] : NIL;
-    for (uint32_t i = tid; i < (uint32_t)MAX_EDGE_CH; i += BLOCK)
-      P.edge_tables[(size_t)q * MAX_EDGE_CH + i] = i < S.edge_chunks ? S.edge_tbl[i] : NIL;
+      }, SpecCounts{}, t_begin);
+    publish_chunk_tables(Q, q, tid);
     __syncthreads();
   }
 }

@@ -1,6 +1,6 @@
 // mplx_poly_search.h -- astar_poly_kernel: GraphSearch::Astar over the moving-obstacle environment (env_poly_map),
-// one workgroup per query, device resident like astar_kernel (mplx_kernels.h) whose OPEN structure, state-space
-// pools, hash table, commit and recoverTraj it shares.  What differs from the voxel environment:
+// one workgroup per query, on the OPEN structure, state-space pools, hash table and commit of mplx_kernels.h and the
+// per-query steps of mplx_search_steps.h.  What differs from the voxel environment:
 //   * get_succ is env_poly_map::get_succ (mplx_poly_dev.h): lane i < n_u builds primitive i, the (primitive,
 //     obstacle) pairs are spread over the lanes, one collide() each;
 //   * successors carry time: tn.t = curr.t + dt and enable_t (env_poly_map.h:63-64), so the state key has one more
@@ -129,73 +129,19 @@ __global__ __launch_bounds__(BLOCK) void astar_poly_kernel(SearchParams P) {
     PolyWorld W;
     poly_stage_world<BLOCK>(DG, WG, wlds, tid, D, W);
     if (tid < P.n_u) { pU[tid][0] = D.U[2 * tid]; pU[tid][1] = D.U[2 * tid + 1]; }  // (read after the __syncthreads() that follow)
-    for (int i = tid; i < 2 * NB; i += BLOCK) S.cnt[0][i] = 0;
+    query_reset(Q, in, (uint32_t)P.n_u, tid);
     if (tid == 0) {
-      S.n_near = 0; S.n_nodes = 0; S.n_edges = 0; S.n_log = 0;
-      S.reserve = (uint32_t)P.n_u;
-      S.node_chunks = S.edge_chunks = S.open_chunks = 0;
-      S.cur1 = 0; S.cur0 = 0; S.lo1 = 0.0; S.ts_f = INFINITY; S.ts_g = INFINITY; S.ts_id = 0xFFFFFFFFu;
-      S.status = -1;
-      for (int i = 0; i < 10; i++) S.cyc[i] = 0;
-      S.c_expanded = S.c_closed = S.c_prims = S.c_succ = S.c_succ_finite = S.c_reads = 0;
-      S.c_push = S.c_reopen = S.c_refill = S.c_evict = 0;
-      S.c_hash = 0;
       punsupported = 0;
       plevel[0] = 0ull; plevel[1] = 0ull;
-      S.hp.w = P.w; S.hp.v_max = P.v_max; S.hp.heur_ignore_dynamics = P.heur_ignore_dynamics;
-      S.hp.goal_control = in.goal_control;
-      S.hp.goal = in.goal;
-      S.hp.goal_nkey = state_key(in.goal_control, in.goal, S.hp.goal_key);
-      double cost0 = INFINITY;
-      if (!poly_inside(W.bbox, 4, in.start.p[0], in.start.p[1]))
-        S.status = 2;  // ENV_->is_free(start.pos) failed
-      else if (in.start_t >= P.t_max || is_goal_state(in.start, in.goal, in.goal_control, P.tol_pos, P.tol_vel, P.tol_acc)) {
-        S.status = 0;
-        cost0 = 0.0;
-      }
-      S.tmp_d0 = cost0;
-      if (S.status < 0) {
-        bool ok = ensure_chunks(S.node_tbl, S.node_chunks, 1, NODE_CH_LOG, MAX_NODE_CH, P.chunk_next + 0, P.node_chunks) &&
-                  ensure_chunks(S.open_tbl, S.open_chunks, 1, OPEN_CH_LOG, MAX_OPEN_CH, P.chunk_next + 2, P.open_chunks);
-        if (!ok) S.status = 4;
-      }
+      // ENV_->is_free(start.pos): inside the bounding box
+      query_admit(Q, in, poly_inside(W.bbox, 4, in.start.p[0], in.start.p[1]), is_goal_state(in.start, in.goal, in.goal_control, P.tol_pos, P.tol_vel, P.tol_acc));
     }
     __syncthreads();
     uint32_t goal_id = NIL;
     if (S.status < 0) {
-      if (tid == 0) {  // start node (id 0); its key carries the start time
-        int32_t key[MAX_KEY];
-        state_key_c<CONTROL>(in.start, key);
-        key[ns] = (int32_t)round(in.start_t / 0.1);
-        char *rec = Q.node(0);
-        for (int i = 0; i < NK; i++) V::key(rec)[i] = key[i];
-        const double *src = (const double *)&in.start;
-        for (int i = 0; i < ns; i++) V::state(rec)[i] = src[i];
-        V::state(rec)[ns] = in.start_t;
-        double h = P.eps == 0.0 ? 0.0 : get_heur(S.hp, CONTROL, in.start, key, NK);
-        V::h(rec) = h;
-        V::g(rec) = 0.0;
-        V::flags(rec) = FLAG_OPENED;
-        V::pred(rec) = NIL;
-        const unsigned long long h64 = key_hash64(key, NK);
-        const unsigned long long tagq = tbl_tagq(h64, (uint32_t)q, P.tbl_epoch);
-        size_t pos = (size_t)(h64 ^ ((unsigned long long)(uint32_t)q * 0x9E3779B97F4A7C15ull)) & (size_t)P.table_mask;
-        for (unsigned long long steps = 0;; steps++) {
-          const unsigned long long seen = ld_u64(&P.table[pos]);  // (a slot of another epoch is empty: claimed against the value seen)
-          if (tbl_empty(seen, P.tbl_epoch) && atomicCAS(&P.table[pos], seen, tagq | 0ull) == seen) break;
-          if (steps > P.table_mask) { S.status = 5; break; }  // (the table is full: never with the host's sizing)
-          pos = (pos + 1) & (size_t)P.table_mask;
-        }
-        S.n_nodes = 1;
-        S.f_base = 0.0 + P.eps * h;
-        S.lo1 = S.f_base;
-        S.n_log = 1;
-        S.c_push = 1;
-      }
-      __syncthreads();
-      if (tid == 0) open_push(Q, 0u, S.f_base, 0.0, 0u);
-      __syncthreads();
-      for (;;) {
+      // (the start's key carries the start time)
+      const bool started = query_start<NK, 0>(Q, in, q, tid, (int32_t)round(in.start_t / 0.1), 0.0, [&](const int32_t *key) { return get_heur(S.hp, CONTROL, in.start, key, NK); });
+      if (started) for (;;) {
         while (S.n_near + S.reserve > (uint32_t)NC) {
           evict_half(Q, tid);
           __syncthreads();
@@ -297,23 +243,10 @@ __global__ __launch_bounds__(BLOCK) void astar_poly_kernel(SearchParams P) {
             if (punsupported) S.status = 5;
           }
         }
-        S.dupset[tid] = 0;
-        S.dupset[tid + BLOCK] = 0;
-        __syncthreads();
         MPLX_TOC(S, 1, tx);
         MPLX_TIC(tc);
+        dup_probe<BLOCK>(S, act, h64, tid);  // (its first barrier publishes the status)
         if (S.status >= 0) break;
-        if (act) {
-          const unsigned long long hv = h64 | 1ull;
-          uint32_t sl = (uint32_t)(h64 >> 7) & (2 * BLOCK - 1);
-          for (;;) {
-            unsigned long long old = atomicCAS(&S.dupset[sl], 0ull, hv);
-            if (old == 0ull) break;
-            if (old == hv) { S.flag = 1; break; }
-            sl = (sl + 1) & (2 * BLOCK - 1);
-          }
-        }
-        __syncthreads();
         if (!S.flag) {
           commit_parallel<BLOCK, CONTROL, Smem<BLOCK>, NK, false, decltype(publish)>(Q, tid, q, act, L, h64, lane_cost, (uint32_t)tid, true, v0, publish);
         } else {
@@ -327,99 +260,23 @@ __global__ __launch_bounds__(BLOCK) void astar_poly_kernel(SearchParams P) {
         __syncthreads();
         MPLX_TOC(S, 2, tc);
         if (S.status >= 0) break;
-        if (tid == 0) {
-          State s;
-          for (int i = 0; i < 12; i++) ((double *)&s)[i] = S.cur[0][i];
-          if (S.cur[0][12] >= P.t_max || is_goal_state(s, S.hp.goal, S.hp.goal_control, P.tol_pos, P.tol_vel, P.tol_acc))  // (the LDS copy of the goal)
-            S.status = 0;
-          else if (P.max_expand > 0 && S.c_expanded >= (unsigned long long)P.max_expand)
-            S.status = 3;
-          else if ((S.c_expanded & 63ull) == 0ull) {  // launch guard: heartbeat + abort word, every 64th expansion
-            guard_mark(P, GUARD_BATCH, (uint32_t)q, S.c_expanded, (unsigned long long)S.n_nodes);
-            if (guard_abort(P)) S.status = PLAN_ABORTED;
-          }
-        }
-        __syncthreads();
-        if (S.status >= 0) break;
+        if (search_ended(Q, q, tid, [&](const State &s) { return is_goal_state(s, S.hp.goal, S.hp.goal_control, P.tol_pos, P.tol_vel, P.tol_acc); })) break;
       }
       goal_id = S.cur_id;
       clear_buckets(Q, tid);
     }
     if (n_help > 0 && tid == 0) st_u64(&DG.help_pub[blockIdx.x], POLY_PUB_DONE | (unsigned long long)S.n_nodes);  // the helpers of this leader leave
     __syncthreads();
-    if (tid == 0) {  // recoverTraj + results
-      QueryOut &o = P.out[q];
-      int32_t *tn = P.traj_nodes + (size_t)q * (MAX_TRAJ + 1);
-      int32_t *ta = P.traj_actions + (size_t)q * MAX_TRAJ;
-      double *ts = P.traj_states + (size_t)q * (MAX_TRAJ + 1) * 13;
-      int status = S.status;
-      double cost = INFINITY;
-      int len = 0;
-      auto edge_cost = [&](uint32_t parent, uint32_t action) {  // calculate_intrinsic_cost of Primitive(parent, U[action], dt)
+    if (tid == 0)  // recoverTraj + results
+      query_report<0>(Q, q, goal_id, [&](uint32_t parent, uint32_t action) {  // calculate_intrinsic_cost of Primitive(parent, U[action], dt)
         const double *st = V::state(Q.node(parent));
-        const double pos[2] = {st[0], st[1]}, vel[2] = {st[3], st[4]}, acc[2] = {CONTROL == CTRL_JRK ? st[6] : 0.0, CONTROL == CTRL_JRK ? st[7] : 0.0}, u[2] = {D.U[2 * action], D.U[2 * action + 1]};
+        const uint32_t a = action & EDGE_ACTION_MASK;
+        const double pos[2] = {st[0], st[1]}, vel[2] = {st[3], st[4]}, acc[2] = {CONTROL == CTRL_JRK ? st[6] : 0.0, CONTROL == CTRL_JRK ? st[7] : 0.0}, u[2] = {D.U[2 * a], D.U[2 * a + 1]};
         double c[2][6];
         poly_prim_build(CONTROL, pos, vel, u, c, acc);
         return poly_intrinsic_cost(CONTROL, c, P.dt, P.w, P.dt);
-      };
-      if (status == 0 && goal_id == NIL) {
-        cost = S.tmp_d0;
-      } else if (status == 0) {
-        uint32_t node = goal_id;
-        tn[0] = (int32_t)node;
-        bool ok = true, too_long = false;
-        while (V::pred(Q.node(node)) != NIL) {
-          uint32_t best = NIL;
-          double min_rhs = INFINITY, min_g = INFINITY;
-          uint32_t hops = 0;
-          for (uint32_t e = V::pred(Q.node(node)); e != NIL && hops <= S.n_edges; e = Q.edge(e)->next, hops++) {
-            const EdgeRec er = *Q.edge(e);
-            double gp = V::g(Q.node(er.parent));
-            double rhs = gp + edge_cost(er.parent, er.action);
-            if (rhs < min_rhs || (rhs == min_rhs && gp >= min_g)) { min_rhs = rhs; min_g = gp; best = e; }
-          }
-          if (best == NIL) { ok = false; break; }
-          if (len >= MAX_TRAJ) { too_long = true; break; }
-          ta[len] = (int32_t)Q.edge(best)->action;
-          node = Q.edge(best)->parent;
-          len++;
-          tn[len] = (int32_t)node;
-          if (node == 0u) break;
-        }
-        if (too_long) {
-          cost = V::g(Q.node(goal_id));
-          status = 6;
-          len = 0;
-        } else if (ok) {
-          cost = V::g(Q.node(goal_id));
-          for (int i = 0; i <= len; i++) {
-            const double *st = V::state(Q.node((uint32_t)tn[i]));
-            for (int k = 0; k < 12; k++) ts[i * 13 + k] = k < ns ? st[k] : 0.0;
-            ts[i * 13 + 12] = st[ns];
-          }
-        } else {
-          status = 1;
-          len = 0;
-        }
-      }
-      o.status = status;
-      o.traj_len = len;
-      o.cost = cost;
-      o.n_expanded = S.c_expanded; o.n_closed = S.c_closed; o.n_nodes = S.n_nodes; o.n_edges = S.n_edges;
-      o.n_primitives = S.c_prims; o.n_succ = S.c_succ; o.n_succ_finite = S.c_succ_finite; o.voxel_reads = 0;
-      o.n_push = S.c_push; o.n_reopen = S.c_reopen; o.n_refill = S.c_refill; o.n_evict = S.c_evict;
-      o.expand_hash = S.c_hash;
-      o.n_recorded = (uint32_t)(S.c_expanded < P.cap_rec ? S.c_expanded : P.cap_rec);
-      o.slot = blockIdx.x;
-      o.spec[0] = o.spec[1] = o.spec[2] = o.spec[3] = 0;
-      o.t_begin = t_begin;
-      o.t_end = wall_clock64();
-      for (int i = 0; i < 10; i++) o.cyc[i] = S.cyc[i];
-    }
-    for (uint32_t i = tid; i < (uint32_t)MAX_NODE_CH; i += BLOCK)
-      P.node_tables[(size_t)q * MAX_NODE_CH + i] = i < S.node_chunks ? S.node_tbl[i] : NIL;
-    for (uint32_t i = tid; i < (uint32_t)MAX_EDGE_CH; i += BLOCK)
-      P.edge_tables[(size_t)q * MAX_EDGE_CH + i] = i < S.edge_chunks ? S.edge_tbl[i] : NIL;
+      }, SpecCounts{}, t_begin);
+    publish_chunk_tables(Q, q, tid);
     __syncthreads();
   }
 }

@@ -665,25 +665,16 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
     const int q = P.order[qi];
     const QueryIn &in = P.queries[q];
     const unsigned long long t_begin = wall_clock64();
-    // ---- reset the workgroup's OPEN structure
-    for (int i = tid; i < 2 * NB; i += BLOCK) S.cnt[0][i] = 0;
+    // ---- reset the workgroup's OPEN structure, then what the batches add to it
+    query_reset(Q, in, (uint32_t)(K * P.n_u + K), tid);
     if (tid == 0) {
-      S.n_near = 0; S.n_nodes = 0; S.n_edges = 0; S.n_log = 0;
-      S.reserve = (uint32_t)(K * P.n_u + K);
       S.n_sorted = 0;
-      S.node_chunks = S.edge_chunks = S.open_chunks = 0;
-      S.cur1 = 0; S.cur0 = 0; S.lo1 = 0.0; S.ts_f = INFINITY; S.ts_g = INFINITY; S.ts_id = 0xFFFFFFFFu;
-      S.status = -1;
-      for (int i = 0; i < 10; i++) S.cyc[i] = 0;
 #ifdef MPLX_LOOKUP_TIMERS
       for (int i = 0; i < 24; i++) S.cyc2[i] = 0;
       for (int i = 0; i < 64; i++) (&S.cycw[0][0])[i] = 0;
       S.arr_max = 0; S.arr_heur = 0; S.sum_heur = 0; S.sum_arr = 0;
       S.dbg_n = S.dbg_na = S.dbg_slow = S.dbg_n256 = S.dbg_pulls = 0;
 #endif
-      S.c_expanded = S.c_closed = S.c_prims = S.c_succ = S.c_succ_finite = S.c_reads = 0;
-      S.c_push = S.c_reopen = S.c_refill = S.c_evict = 0;
-      S.c_hash = 0;
       S.c_cand = S.c_live = S.c_cut = 0;
       S.cur_id = NIL;
       S.helped = 0;
@@ -701,75 +692,20 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
         st_u64(&box->n_expanded, 0ull);
         st_u64(&box->seq, ((unsigned long long)P.epoch << 32) | 1ull);
       }
-      S.hp.w = P.w; S.hp.v_max = P.v_max; S.hp.heur_ignore_dynamics = P.heur_ignore_dynamics;
-      S.hp.goal_control = in.goal_control;
-      S.hp.goal = in.goal;
-      S.hp.goal_nkey = state_key(in.goal_control, in.goal, S.hp.goal_key);
-      S.hp.goal_yaw = in.goal_yaw;
-      S.hp.goal_yaw_key = (int32_t)round(in.goal_yaw / KEY_RES_YAW);
-      int32_t c[3];
-      bool free_ = true;
-      for (int ax = 0; ax < 3; ax++) {
-        c[ax] = float_to_cell(in.start.p[ax], P.map.origin[ax], P.map.res);
-        if (c[ax] < 0 || c[ax] >= P.map.dim[ax]) free_ = false;
-      }
-      if (free_) free_ = P.map.data[(size_t)c[0] + (size_t)P.map.dim[0] * c[1] + (size_t)P.map.dim[0] * P.map.dim[1] * c[2]] == 0;
-      double cost0 = INFINITY;
-      if (!free_)
-        S.status = 2;
-      else if (in.start_t >= P.t_max || goal_reached(in.start, in.start_yaw)) {
-        S.status = 0;
-        cost0 = 0.0;
-      }
-      S.tmp_d0 = cost0;
-      if (S.status < 0) {
-        bool ok = Q.ensure_nodes(1) &&
-                  Q.ensure_open(1);
-        if (!ok) S.status = 4;
-      }
+      query_admit(Q, in, voxel_start_free(P, in), goal_reached(in.start, in.start_yaw));
     }
     __syncthreads();
     bool searched = false;
     if (S.status < 0) {
       searched = true;
-      // ---- start node (id 0)
-      if (tid == 0) {
-        int32_t key[MAX_KEY + 1];
-        state_key_c<CONTROL>(in.start, key);
-        const int32_t ykey = (int32_t)round(in.start_yaw / KEY_RES_YAW);
-        if (YAW) key[nk] = ykey;
-        char *rec = Q.node(0);
-        for (int i = 0; i < NKY; i++) V::key(rec)[i] = key[i];
-        const double *src = (const double *)&in.start;
-        for (int i = 0; i < ns; i++) {
-          if constexpr (HELP) st_f64_agent(&V::state(rec)[i], src[i]); else V::state(rec)[i] = src[i];
-        }
-        if (YAW) V::state(rec)[ns] = in.start_yaw;
-        V::state(rec)[ns + EX] = in.start_t;
-        double h = 0.0;
-        if (P.eps != 0.0) h = (YAW && ykey != S.hp.goal_yaw_key) ? cal_heur(S.hp, CONTROL, in.start) : get_heur(S.hp, CONTROL, in.start, key, nk);
-        V::h(rec) = h;
-        V::g(rec) = 0.0;
-        V::flags(rec) = FLAG_OPENED;
-        V::pred(rec) = NIL;
-        const unsigned long long h64 = key_hash64(key, NKY);
-        const unsigned long long tagq = tbl_tagq(h64, (uint32_t)q, P.tbl_epoch);
-        size_t pos = (size_t)(h64 ^ ((unsigned long long)(uint32_t)q * 0x9E3779B97F4A7C15ull)) & (size_t)P.table_mask;
-        for (unsigned long long steps = 0;; steps++) {
-          const unsigned long long seen = ld_u64(&P.table[pos]);  // (a slot of another epoch is empty: claimed against the value seen)
-          if (tbl_empty(seen, P.tbl_epoch) && atomicCAS(&P.table[pos], seen, tagq | 0ull) == seen) break;
-          if (steps > P.table_mask) { S.status = 5; break; }  // (the table is full: never with the host's sizing)
-          pos = (pos + 1) & (size_t)P.table_mask;
-        }
-        S.n_nodes = 1;
-        S.f_base = 0.0 + P.eps * h;
-        S.lo1 = S.f_base;
-        S.n_log = 1;
-        S.c_push = 1;
-      }
-      __syncthreads();
-      if (tid == 0) open_push(Q, 0u, S.f_base, 0.0, 0u);
-      __syncthreads();
+      // ---- start node (id 0); its state doubles written through in the HELP builds, like every node's
+      const int32_t ykey = (int32_t)round(in.start_yaw / KEY_RES_YAW);
+      // (its result is not tested: a guard on the batch loop's entry changed the loop's register allocation -- the kernel sits at the
+      // register limit -- and cost 5-9 % of kernel time.  Where the start node found no table slot, status 5, never with the host's
+      // sizing, nothing was pushed and the first batch ends the query on its empty OPEN list.)
+      query_start<NKY, EX>(Q, in, q, tid, ykey, in.start_yaw, [&](const int32_t *key) {
+        return (YAW && ykey != S.hp.goal_yaw_key) ? cal_heur(S.hp, CONTROL, in.start) : get_heur(S.hp, CONTROL, in.start, key, nk);
+      }, [](double *p, double v) { if constexpr (HELP) st_f64_agent(p, v); else *p = v; });
       // ---- main loop: one batch of up to K expansions per iteration
       // far-bucket link whose atomicExch (an HBM round trip) is still in flight: open(pend_idx)->next = pend_old is
       // stored at the top of the NEXT iteration -- nothing walks a far list before that -- so the round trip
@@ -1802,68 +1738,9 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
     __syncthreads();
     // ---- recoverTraj + results (thread 0)
     if (tid == 0) {
-      QueryOut &o = P.out[q];
-      int32_t *tn = P.traj_nodes + (size_t)q * (MAX_TRAJ + 1);
-      int32_t *ta = P.traj_actions + (size_t)q * MAX_TRAJ;
-      double *ts = P.traj_states + (size_t)q * (MAX_TRAJ + 1) * 13;
-      int status = S.status;
-      double cost = INFINITY;
-      int len = 0;
-      if (status == 0 && goal_id == NIL) {
-        cost = S.tmp_d0;
-      } else if (status == 0) {
-        uint32_t node = goal_id;
-        tn[0] = (int32_t)node;
-        bool ok = true, too_long = false;
-        while (V::pred(Q.node(node)) != NIL) {
-          uint32_t best = NIL;
-          double min_rhs = INFINITY, min_g = INFINITY;
-          uint32_t hops = 0;
-          for (uint32_t e = V::pred(Q.node(node)); e != NIL && hops <= S.n_edges; e = Q.edge(e)->next, hops++) {
-            const EdgeRec er = *Q.edge(e);
-            double gp = V::g(Q.node(er.parent));
-            const double ec = (POT && P.map.aux) ? P.ucost[er.action & EDGE_ACTION_MASK] + P.pot_weight * (double)(er.action >> EDGE_POT_SHIFT) : P.ucost[er.action & EDGE_ACTION_MASK];
-            double rhs = gp + ec;
-            if (rhs < min_rhs || (rhs == min_rhs && gp >= min_g)) { min_rhs = rhs; min_g = gp; best = e; }
-          }
-          if (best == NIL) { ok = false; break; }
-          if (len >= MAX_TRAJ) { too_long = true; break; }
-          ta[len] = (int32_t)(Q.edge(best)->action & EDGE_ACTION_MASK);
-          node = Q.edge(best)->parent;
-          len++;
-          tn[len] = (int32_t)node;
-          if (node == 0u) break;
-        }
-        if (too_long) {  // goal reached and cost known; the path does not fit the device-side buffer
-          cost = V::g(Q.node(goal_id));
-          status = 6;    // MPLX_PLAN_TRAJ_TOO_LONG
-          len = 0;
-        } else if (ok) {
-          cost = V::g(Q.node(goal_id));
-          for (int i = 0; i <= len; i++) {
-            const double *st = V::state(Q.node((uint32_t)tn[i]));
-            for (int k = 0; k < 12; k++) ts[i * 13 + k] = k < ns ? ld_state(&st[k]) : 0.0;
-            ts[i * 13 + 12] = ld_state(&st[ns + EX]);
-            if (YAW && P.traj_yaw) P.traj_yaw[(size_t)q * (MAX_TRAJ + 1) + i] = st[ns];
-          }
-        } else {
-          status = 1;
-          len = 0;
-        }
-      }
-      o.status = status;
-      o.traj_len = len;
-      o.cost = cost;
-      o.n_expanded = S.c_expanded; o.n_closed = S.c_closed; o.n_nodes = S.n_nodes; o.n_edges = S.n_edges;
-      o.n_primitives = S.c_prims; o.n_succ = S.c_succ; o.n_succ_finite = S.c_succ_finite; o.voxel_reads = S.c_reads;
-      o.n_push = S.c_push; o.n_reopen = S.c_reopen; o.n_refill = S.c_refill; o.n_evict = S.c_evict;
-      o.expand_hash = S.c_hash;
-      o.n_recorded = (uint32_t)(S.c_expanded < P.cap_rec ? S.c_expanded : P.cap_rec);
-      o.slot = blockIdx.x;
-      o.spec[0] = S.c_cand; o.spec[1] = S.c_cand - S.c_live; o.spec[2] = S.c_live; o.spec[3] = S.c_cut;
-      o.t_begin = t_begin;
-      o.t_end = wall_clock64();
-      for (int i = 0; i < 10; i++) o.cyc[i] = S.cyc[i];
+      query_report<EX>(Q, q, goal_id, [&](uint32_t, uint32_t action) {
+        return (POT && P.map.aux) ? P.ucost[action & EDGE_ACTION_MASK] + P.pot_weight * (double)(action >> EDGE_POT_SHIFT) : P.ucost[action & EDGE_ACTION_MASK];
+      }, SpecCounts{{S.c_cand, S.c_cand - S.c_live, S.c_live, S.c_cut}}, t_begin, ld_state);
 #ifdef MPLX_LOOKUP_TIMERS
       if (P.nq == 1 || q % 61 == 0) {  // (a batch: a sample of its queries -- a thousand workgroups printing at once tear each other's lines)
       printf("cyc2 q%d batches %llu:", q, S.cyc[7]);
@@ -1922,11 +1799,7 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
         for (uint32_t i = tid; i < S.open_chunks; i += BLOCK) Q.chunk_give(2, Q.open_chunk(i));
       }
     }
-    // chunk tables of the query for the host's state-space getters (a recycling launch keeps no state space: the host refuses them)
-    for (uint32_t i = tid; i < (uint32_t)MAX_NODE_CH; i += BLOCK)
-      P.node_tables[(size_t)q * MAX_NODE_CH + i] = (i < S.node_chunks && !P.chunk_bits) ? Q.node_chunk(i) : NIL;
-    for (uint32_t i = tid; i < (uint32_t)MAX_EDGE_CH; i += BLOCK)
-      P.edge_tables[(size_t)q * MAX_EDGE_CH + i] = (i < S.edge_chunks && !P.chunk_bits) ? Q.edge_chunk(i) : NIL;
+    publish_chunk_tables(Q, q, tid, !P.chunk_bits);
     if constexpr (HELP) {
       if (tid == 0) atomicAdd(P.done_word, 1ull);
     }
