@@ -362,6 +362,35 @@ int mplx_lpa_result_edges(mplx_lpa *l, int32_t *child, int32_t *parent, int32_t 
 int mplx_lpa_result_expanded(mplx_lpa *l, uint32_t cap, int32_t *ids, uint32_t *n);
 int mplx_lpa_last_kernel_ms(const mplx_lpa *l, float *ms);
 
+/* ---- LPA* fleets: N planners on ctx's map and planner set-up (N robots that each keep a state space on one shared, changing
+ *      map) whose plan() and map updates run for all members at once.  A member is an ordinary mplx_lpa -- every mplx_lpa_* getter
+ *      and setter works on it, and so does mplx_lpa_plan on a single member -- owned by the fleet (mplx_lpa_destroy ignores it).
+ *      Per member every result is what the same sequence of single-handle calls gives.  The members share ONE import lane. ---- */
+typedef struct mplx_lpa_fleet mplx_lpa_fleet;
+int mplx_lpa_fleet_create(mplx_ctx *ctx, int32_t n, mplx_lpa_fleet **out);  /* no device work; destroy it before ctx */
+void mplx_lpa_fleet_destroy(mplx_lpa_fleet *f);
+const char *mplx_lpa_fleet_last_error(const mplx_lpa_fleet *f);
+int mplx_lpa_fleet_size(const mplx_lpa_fleet *f);
+mplx_lpa *mplx_lpa_fleet_member(mplx_lpa_fleet *f, int32_t i);  /* borrowed */
+int mplx_lpa_fleet_set_capacity(mplx_lpa_fleet *f, uint64_t nodes, uint64_t edges, uint64_t open_log);  /* per member (0 = keep) */
+/* plan() of every member i with active[i] != 0 (NULL: all) from starts[i] to goals[i]; out: n results (zeroed for an inactive
+ * member, whose space and stored trajectory stay).  Decided per member as mplx_lpa_plan decides: the members whose space, set-up,
+ * goal and root are unchanged are REPAIRED in one launch, one workgroup each; a member that needs a fresh plan takes
+ * mplx_lpa_plan's path, one member after the other.  A per-member outcome (MPLX_PLAN_POOL_FULL, an occupied start, a start at the
+ * goal) ends that member only; what mplx_lpa_plan refuses is refused for the whole call before any launch.  A launch aborted by
+ * the deadline invalidates every member that was in it (MPLX_ERR_TIMEOUT). */
+int mplx_lpa_fleet_plan(mplx_lpa_fleet *f, const mplx_waypoint *starts, const mplx_waypoint *goals, const int32_t *active, mplx_result *out);
+/* mplx_lpa_update_blocked / _cleared of every member that holds a state space, one launch per pass.  n_changed (n entries, or
+ * NULL): per member; a member whose conversion ran out of pool is dropped alone (n_changed[i] = ~0, MPLX_ERR_CAPACITY). */
+int mplx_lpa_fleet_update_blocked(mplx_lpa_fleet *f, int n_cells, const int32_t *cells, uint64_t *n_changed);
+int mplx_lpa_fleet_update_cleared(mplx_lpa_fleet *f, int n_cells, const int32_t *cells, uint64_t *n_changed);
+/* mplx_lpa_sub_state_space(member i, time_step[i]), one member after the other; time_step[i] < 0 leaves the member alone */
+int mplx_lpa_fleet_sub_state_space(mplx_lpa_fleet *f, const int32_t *time_step);
+/* the last mplx_lpa_fleet_plan: [0] members repaired in the fleet launch, [1] search launches that took (1, or 0 when nobody
+ * repaired), [2] members planned afresh, [3] members skipped (inactive) */
+int mplx_lpa_fleet_stats(const mplx_lpa_fleet *f, uint32_t stats[4]);
+int mplx_lpa_fleet_last_kernel_ms(const mplx_lpa_fleet *f, float *repair_ms, float *fresh_ms);
+
 /* ---- VoxelGrid (planning_ros_utils/src/mapping_utils/voxel_grid.cpp, the mapper in front of the planner:
  *      map_replanner_node.cpp:17,181,218,329-331, cloud_to_map.cpp:11-12).  Device-resident; same
  *      semantics as the in-tree class: float resolution, truncating floatToInt (:201-203), two grids

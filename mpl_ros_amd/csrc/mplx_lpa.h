@@ -42,9 +42,42 @@ struct LpaParams {
   const char *old_node_pool;
   const unsigned long long *old_table;
   unsigned long long old_table_mask;
-  const LpaState *old_st;
+  union {
+    const LpaState *old_st;
+    // FLEET builds of lpa_plan_kernel / lpa_update_kernel (they never re-root): one descriptor per workgroup row.  It shares the
+    // word of old_st so that the struct -- and with it the argument layout of every single-planner kernel -- stays as it was.
+    const struct LpaMember *members;
+  };
   int32_t time_step;
 };
+// A fleet is N planners on ONE map and planner set-up whose repairs and map edits run in one launch (mplx_lpa_fleet_*): what
+// differs between the members comes from this descriptor (device memory, read once per workgroup; the loads are uniform), the
+// map, the lattice, the limits and the launch guard are the launch's SearchParams.
+struct LpaMember {
+  char *node_pool, *edge_pool, *open_pool;
+  unsigned long long *table;
+  unsigned long long table_mask;
+  uint32_t *bkt_head;
+  LpaState *st;
+  uint2 *blocked_log;
+  const QueryIn *query;
+  QueryOut *out;
+  int32_t *traj_nodes, *traj_actions;
+  double *traj_states;
+  int32_t *rec_ids;
+  uint32_t node_chunks, edge_chunks, open_chunks, cap_rec, blocked_cap, pad;
+};
+__device__ __forceinline__ void lpa_member_args(SearchParams &P, LpaParams &A, const LpaMember &m) {
+  P.node_pool = m.node_pool; P.edge_pool = m.edge_pool; P.open_pool = m.open_pool;
+  P.table = m.table; P.table_mask = m.table_mask;
+  P.bkt_head = m.bkt_head;
+  P.queries = m.query; P.out = m.out;
+  P.traj_nodes = m.traj_nodes; P.traj_actions = m.traj_actions; P.traj_states = m.traj_states;
+  P.rec_ids = m.rec_ids;
+  P.node_chunks = m.node_chunks; P.edge_chunks = m.edge_chunks; P.open_chunks = m.open_chunks;
+  P.cap_rec = m.cap_rec;
+  A.st = m.st; A.blocked_log = m.blocked_log; A.blocked_cap = m.blocked_cap;
+}
 
 template <int BLOCK, int CONTROL>
 struct LView : QView<BLOCK, CONTROL> {
@@ -347,8 +380,10 @@ __device__ __forceinline__ void lpa_dup_check(Smem<BLOCK> &S, int tid, bool act,
 }
 
 // ------------------------------------------------------------------ ComputeShortestPath
-template <int BLOCK, int CONTROL>
+// FLEET: the search of member blockIdx.x of a fleet (LpaMember); one workgroup per member, no dependency between them
+template <int BLOCK, int CONTROL, bool FLEET = false>
 __global__ __launch_bounds__(BLOCK) void lpa_plan_kernel(SearchParams P, LpaParams A) {
+  if constexpr (FLEET) lpa_member_args(P, A, A.members[blockIdx.x]);
   __shared__ Smem<BLOCK> S;
   __shared__ uint32_t s_nblk, s_gid, s_root;
   __shared__ int32_t s_stop;
@@ -762,8 +797,10 @@ __global__ __launch_bounds__(BLOCK) void lpa_plan_kernel(SearchParams P, LpaPara
 //           the order of the entries are results): one thread
 //   pass 2  updateNode of the flagged states, grid-stride again
 // The passes are separate launches: what pass 0 writes (entry flags, state flags) is read by other workgroups in pass 2.
-template <int BLOCK, int CONTROL>
+// FLEET: the member in blockIdx.y, the grid-stride over blockIdx.x inside it
+template <int BLOCK, int CONTROL, bool FLEET = false>
 __global__ __launch_bounds__(BLOCK) void lpa_update_kernel(SearchParams P, LpaParams A, int mode, int pass) {
+  if constexpr (FLEET) lpa_member_args(P, A, A.members[blockIdx.y]);
   __shared__ Smem<BLOCK> S;
   using V = LView<BLOCK, CONTROL>;
   const int tid = threadIdx.x;

@@ -15,6 +15,29 @@ struct LpaSpace {
   LpaState *st = nullptr;
 };
 
+// A FRESH plan is an A* from scratch: planned by the speculative kernel on a lane context (the parent's map replica and planner
+// set-up, like a lane of an mplx_stream) and imported into the LPA* pools (mplx_lpa.h "import of a finished A*").  The lane holds pools
+// of an LPA* handle's capacity: a handle owns one, the members of a fleet share one.
+struct LpaLane {
+  mplx_ctx *imp = nullptr;
+  uint64_t imp_map_epoch = 0;
+  // what the lane was last configured for (lpa_import_lane): the parent's cfg_epoch, 1 plan / 2 Dijkstra, the handle's capacities
+  uint64_t imp_cfg_epoch = ~0ull;
+  int imp_mode = 0;
+  uint64_t imp_cap_nodes = 0, imp_cap_edges = 0, imp_cap_log = 0;
+  uint32_t *d_blk_off = nullptr;
+  unsigned long long *d_blk_mask = nullptr;
+  size_t blk_cap = 0;
+  hipEvent_t imp_ev0 = nullptr, imp_ev1 = nullptr;
+};
+static void lpa_lane_free(LpaLane *ln) {
+  (void)hipFree(ln->d_blk_off); (void)hipFree(ln->d_blk_mask);
+  if (ln->imp_ev0) (void)hipEventDestroy(ln->imp_ev0);
+  if (ln->imp_ev1) (void)hipEventDestroy(ln->imp_ev1);
+  if (ln->imp) mplx_ctx_destroy(ln->imp);
+  *ln = LpaLane();
+}
+
 struct mplx_lpa {
   mplx_ctx *ctx = nullptr;
   std::string err;
@@ -41,24 +64,20 @@ struct mplx_lpa {
   int32_t root_key[MAX_KEY] = {};
   QueryOut last_out{};
   int reroot_mode = 2;  // getSubStateSpace: 0 Dijkstra through the expanded states, 1 plan afresh from the new root, 2 auto (mplx_lpa_set_reroot)
-  // what the import lane was last configured for (lpa_import_lane): the parent's cfg_epoch, 1 plan / 2 Dijkstra, the handle's capacities
-  uint64_t imp_cfg_epoch = ~0ull;
-  int imp_mode = 0;
-  uint64_t imp_cap_nodes = 0, imp_cap_edges = 0, imp_cap_log = 0;
   LpaState st{};                 // host copy of the current space's scalars
   // the last trajectory (getTraj() returns the Trajectory stored at plan time, also after getSubStateSpace)
   int traj_len = 0;
   std::vector<int32_t> traj_nodes, traj_actions;
   std::vector<double> traj_states;
   float last_ms = 0;
-  // a FRESH plan is an A* from scratch: planned by the speculative kernel on a private lane context (the parent's map replica and
-  // planner set-up, like a lane of an mplx_stream) and imported into the LPA* pools (mplx_lpa.h "import of a finished A*")
-  mplx_ctx *imp = nullptr;
-  uint64_t imp_map_epoch = 0;
-  uint32_t *d_blk_off = nullptr;
-  unsigned long long *d_blk_mask = nullptr;
-  size_t blk_cap = 0;
-  hipEvent_t imp_ev0 = nullptr, imp_ev1 = nullptr;
+  // the import lane of the fresh plans: the handle's own, or the one its fleet shares between the members (mplx_lpa_fleet)
+  LpaLane own_lane;
+  LpaLane *ln = &own_lane;
+  // member of a fleet: the fleet owns the handle and the arrays its LpaState / QueryIn / QueryOut are slices of (one copy per fleet call)
+  struct mplx_lpa_fleet *fleet = nullptr;
+  LpaState *fleet_st = nullptr;  // [2]: the two spaces' scalars
+  QueryIn *fleet_in = nullptr;
+  QueryOut *fleet_out = nullptr;
 };
 
 static int lfail(mplx_lpa *l, int code, const char *fmt, ...) {
@@ -79,7 +98,8 @@ static int lfail(mplx_lpa *l, int code, const char *fmt, ...) {
 static void lpa_free_pools(mplx_lpa *l) {
   for (int k = 0; k < 2; k++) {
     (void)hipFree(l->sp[k].node_pool); (void)hipFree(l->sp[k].edge_pool); (void)hipFree(l->sp[k].table);
-    (void)hipFree(l->sp[k].blocked_log); (void)hipFree(l->sp[k].st);
+    (void)hipFree(l->sp[k].blocked_log);
+    if (!l->fleet_st) (void)hipFree(l->sp[k].st);
     l->sp[k] = LpaSpace();
   }
   (void)hipFree(l->open_pool); (void)hipFree(l->bkt_head);
@@ -95,16 +115,14 @@ extern "C" int mplx_lpa_create(mplx_ctx *ctx, mplx_lpa **out) {
   return MPLX_OK;
 }
 extern "C" void mplx_lpa_destroy(mplx_lpa *l) {
-  if (!l) return;
+  if (!l || l->fleet) return;  // (a fleet's member is borrowed: mplx_lpa_fleet_destroy ends it)
   (void)hipSetDevice(l->ctx->device);
   (void)hipStreamSynchronize(l->ctx->stream);
   lpa_free_pools(l);
-  (void)hipFree(l->d_in); (void)hipFree(l->d_out); (void)hipFree(l->d_traj_nodes); (void)hipFree(l->d_traj_actions);
+  if (!l->fleet_st) { (void)hipFree(l->d_in); (void)hipFree(l->d_out); }
+  (void)hipFree(l->d_traj_nodes); (void)hipFree(l->d_traj_actions);
   (void)hipFree(l->d_traj_states); (void)hipFree(l->d_rec);
-  (void)hipFree(l->d_blk_off); (void)hipFree(l->d_blk_mask);
-  if (l->imp_ev0) (void)hipEventDestroy(l->imp_ev0);
-  if (l->imp_ev1) (void)hipEventDestroy(l->imp_ev1);
-  if (l->imp) mplx_ctx_destroy(l->imp);
+  lpa_lane_free(&l->own_lane);
   delete l;
 }
 extern "C" const char *mplx_lpa_last_error(const mplx_lpa *l) { return l ? l->err.c_str() : ""; }
@@ -128,8 +146,13 @@ extern "C" int mplx_lpa_reset(mplx_lpa *l) {
   return MPLX_OK;
 }
 
+static int fleet_ensure(struct mplx_lpa_fleet *f, std::string *why);  // (mplx_lpa_fleet.inl)
 static int lpa_ensure(mplx_lpa *l) {
   mplx_ctx *c = l->ctx;
+  if (l->fleet && !l->fleet_st) {  // (a member used on its own before any fleet call)
+    std::string why;
+    if (int rf = fleet_ensure(l->fleet, &why)) return lfail(l, rf, "%s", why.c_str());
+  }
   const int control = c->cfg.control;
   if (l->pools_valid && l->pool_control == control && l->pool_nodes == l->cap_nodes && l->pool_edges == l->cap_edges && l->pool_log == l->cap_log) {
     if (l->cap_rec > l->rec_alloc) {
@@ -152,14 +175,20 @@ static int lpa_ensure(mplx_lpa *l) {
     LCHK(l, hipMalloc((void **)&l->sp[k].edge_pool, (size_t)(ech << EDGE_CH_LOG) * EDGE_BYTES));
     LCHK(l, hipMalloc((void **)&l->sp[k].table, (size_t)l->table_slots * sizeof(unsigned long long)));
     LCHK(l, hipMalloc((void **)&l->sp[k].blocked_log, (size_t)(ech << EDGE_CH_LOG) * sizeof(uint2)));
-    LCHK(l, hipMalloc((void **)&l->sp[k].st, sizeof(LpaState)));
+    if (l->fleet_st) l->sp[k].st = l->fleet_st + k;
+    else LCHK(l, hipMalloc((void **)&l->sp[k].st, sizeof(LpaState)));
   }
   LCHK(l, hipMalloc((void **)&l->open_pool, (size_t)(och << OPEN_CH_LOG) * OPEN_BYTES));
   LCHK(l, hipMalloc((void **)&l->bkt_head, sizeof(uint32_t) * 2 * NB * NSUB));
   LCHK(l, hipMemsetAsync(l->bkt_head, 0xFF, sizeof(uint32_t) * 2 * NB * NSUB, c->stream));
   if (!l->d_in) {
-    LCHK(l, hipMalloc((void **)&l->d_in, sizeof(QueryIn)));
-    LCHK(l, hipMalloc((void **)&l->d_out, sizeof(QueryOut)));
+    if (l->fleet_st) {
+      l->d_in = l->fleet_in;
+      l->d_out = l->fleet_out;
+    } else {
+      LCHK(l, hipMalloc((void **)&l->d_in, sizeof(QueryIn)));
+      LCHK(l, hipMalloc((void **)&l->d_out, sizeof(QueryOut)));
+    }
     LCHK(l, hipMalloc((void **)&l->d_traj_nodes, sizeof(int32_t) * (MAX_TRAJ + 1)));
     LCHK(l, hipMalloc((void **)&l->d_traj_actions, sizeof(int32_t) * MAX_TRAJ));
     LCHK(l, hipMalloc((void **)&l->d_traj_states, sizeof(double) * (MAX_TRAJ + 1) * 13));
@@ -223,21 +252,21 @@ static bool lpa_same_goal(const mplx_waypoint &a, const mplx_waypoint &b) {
 static int lpa_import_lane(mplx_lpa *l, bool dijkstra) {
   mplx_ctx *c = l->ctx;
   int r;
-  if (!l->imp) {
-    if ((r = mplx_ctx_create(c->device, &l->imp)) != MPLX_OK) return lfail(l, r, "LPA* import lane: %s", g_create_error.c_str());
-    l->imp_map_epoch = 0;
-    LCHK(l, hipEventCreate(&l->imp_ev0));
-    LCHK(l, hipEventCreate(&l->imp_ev1));
+  if (!l->ln->imp) {
+    if ((r = mplx_ctx_create(c->device, &l->ln->imp)) != MPLX_OK) return lfail(l, r, "LPA* import lane: %s", g_create_error.c_str());
+    l->ln->imp_map_epoch = 0;
+    LCHK(l, hipEventCreate(&l->ln->imp_ev0));
+    LCHK(l, hipEventCreate(&l->ln->imp_ev1));
   }
-  mplx_ctx *lane = l->imp;
-  if (l->imp_map_epoch != c->map_epoch || lane->map != c->map) {  // the parent's map changed (or was replaced): adopt it again
+  mplx_ctx *lane = l->ln->imp;
+  if (l->ln->imp_map_epoch != c->map_epoch || lane->map != c->map) {  // the parent's map changed (or was replaced): adopt it again
     if ((r = mplx_map_set_device(lane, c->map, c->dim, c->origin, c->res)) != MPLX_OK) return lfail(l, r, "LPA* import lane: %s", lane->err.c_str());
-    l->imp_map_epoch = c->map_epoch;
+    l->ln->imp_map_epoch = c->map_epoch;
   }
   //  the lane is re-configured -- device buffers of the lattice freed and allocated, a stream synchronisation -- only when the
   // parent's set-up changed since, or when the lane last ran in the other mode (plan / Dijkstra): not on every replanning call
   const int want_mode = dijkstra ? 2 : 1;
-  if (l->imp_cfg_epoch == c->cfg_epoch && l->imp_mode == want_mode && l->imp_cap_nodes == l->cap_nodes && l->imp_cap_edges == l->cap_edges && l->imp_cap_log == l->cap_log) {
+  if (l->ln->imp_cfg_epoch == c->cfg_epoch && l->ln->imp_mode == want_mode && l->ln->imp_cap_nodes == l->cap_nodes && l->ln->imp_cap_edges == l->cap_edges && l->ln->imp_cap_log == l->cap_log) {
     lane->deadline_s = c->deadline_s;
     lane->helpers = c->helpers; lane->help_reserved = c->help_reserved; lane->help_rows = c->help_rows; lane->help_limit = -1;
     return MPLX_OK;
@@ -258,21 +287,21 @@ static int lpa_import_lane(mplx_lpa *l, bool dijkstra) {
   lane->helpers = c->helpers; lane->help_reserved = c->help_reserved; lane->help_rows = c->help_rows; lane->help_limit = -1;
   mplx_set_capacity(lane, 1, l->cap_nodes, l->cap_edges, l->cap_log);
   lane->cap_rec = (uint32_t)std::min<uint64_t>(l->cap_nodes, 0xFFFFFFF0ull);  // every expansion closes a state: the record holds the whole order
-  l->imp_cfg_epoch = c->cfg_epoch;
-  l->imp_mode = want_mode;
-  l->imp_cap_nodes = l->cap_nodes; l->imp_cap_edges = l->cap_edges; l->imp_cap_log = l->cap_log;
+  l->ln->imp_cfg_epoch = c->cfg_epoch;
+  l->ln->imp_mode = want_mode;
+  l->ln->imp_cap_nodes = l->cap_nodes; l->ln->imp_cap_edges = l->cap_edges; l->ln->imp_cap_log = l->cap_log;
   return MPLX_OK;
 }
 // the three import kernels on the lane's stream (P / A: lpa_params of the space written), timed into *ms
 static int lpa_import_launch(mplx_lpa *l, const SearchParams &P, const LpaParams &A, int mode, float *ms) {
-  mplx_ctx *c = l->ctx, *lane = l->imp;
+  mplx_ctx *c = l->ctx, *lane = l->ln->imp;
   const size_t n_exp = lane->last_out[0].n_recorded;
-  if (l->blk_cap < n_exp + 1) {
-    (void)hipFree(l->d_blk_off); (void)hipFree(l->d_blk_mask);
-    l->d_blk_off = nullptr; l->d_blk_mask = nullptr;
-    l->blk_cap = std::max<size_t>(n_exp + 1, (size_t)1 << 16) * 2;
-    LCHK(l, hipMalloc((void **)&l->d_blk_off, sizeof(uint32_t) * l->blk_cap));
-    LCHK(l, hipMalloc((void **)&l->d_blk_mask, sizeof(unsigned long long) * 2 * l->blk_cap));
+  if (l->ln->blk_cap < n_exp + 1) {
+    (void)hipFree(l->ln->d_blk_off); (void)hipFree(l->ln->d_blk_mask);
+    l->ln->d_blk_off = nullptr; l->ln->d_blk_mask = nullptr;
+    l->ln->blk_cap = std::max<size_t>(n_exp + 1, (size_t)1 << 16) * 2;
+    LCHK(l, hipMalloc((void **)&l->ln->d_blk_off, sizeof(uint32_t) * l->ln->blk_cap));
+    LCHK(l, hipMalloc((void **)&l->ln->d_blk_mask, sizeof(unsigned long long) * 2 * l->ln->blk_cap));
   }
   LpaImportArgs I{};
   I.node_pool = lane->pools.node_pool; I.edge_pool = lane->pools.edge_pool;
@@ -280,7 +309,7 @@ static int lpa_import_launch(mplx_lpa *l, const SearchParams &P, const LpaParams
   I.out = lane->d_out;
   I.rec_ids = lane->d_rec;
   I.traj_nodes = lane->d_traj_nodes; I.traj_actions = lane->d_traj_actions; I.traj_states = lane->d_traj_states;
-  I.blk_off = l->d_blk_off; I.blk_mask = l->d_blk_mask;
+  I.blk_off = l->ln->d_blk_off; I.blk_mask = l->ln->d_blk_mask;
   I.dst_rec = (mode == 0 && l->cap_rec) ? l->d_rec : nullptr; I.dst_cap_rec = mode == 0 ? l->cap_rec : 0;
   I.mode = mode;
   if (mode == 1) {  // the heuristic of a state the old space did not hold: the planner's goal
@@ -290,20 +319,20 @@ static int lpa_import_launch(mplx_lpa *l, const SearchParams &P, const LpaParams
     I.hp.goal_nkey = state_key(l->goal.control, I.hp.goal, I.hp.goal_key);
   }
   hipStream_t s = lane->stream;
-  LCHK(l, hipEventRecord(l->imp_ev0, s));
+  LCHK(l, hipEventRecord(l->ln->imp_ev0, s));
   LCHK(l, hipMemsetAsync(P.table, 0xFF, (size_t)l->table_slots * sizeof(unsigned long long), s));
   LCHK(l, hipMemsetAsync(A.st, 0, sizeof(LpaState), s));
   if (!mplx_launch_lpa_import(s, P, A, I, std::max(1, 4 * c->n_cus))) return lfail(l, MPLX_ERR_ARG, "LPA* supports lattices of at most 128 control inputs (got %d)", P.n_u);
   LCHK(l, hipGetLastError());
-  LCHK(l, hipEventRecord(l->imp_ev1, s));
+  LCHK(l, hipEventRecord(l->ln->imp_ev1, s));
   LCHK(l, hipStreamSynchronize(s));  // (short, bounded kernels: copy, one get_succ per expanded state, a scan)
-  LCHK(l, hipEventElapsedTime(ms, l->imp_ev0, l->imp_ev1));
+  LCHK(l, hipEventElapsedTime(ms, l->ln->imp_ev0, l->ln->imp_ev1));
   return MPLX_OK;
 }
 static int lpa_plan_by_import(mplx_lpa *l, const mplx_waypoint *start, const mplx_waypoint *goal, const SearchParams &P, const LpaParams &A) {
   int r;
   if ((r = lpa_import_lane(l, false)) != MPLX_OK) return r;
-  mplx_ctx *lane = l->imp;
+  mplx_ctx *lane = l->ln->imp;
   mplx_result res;
   if ((r = mplx_plan(lane, start, goal, &res)) != MPLX_OK) return lfail(l, r, "%s", lane->err.c_str());
   float imp_ms = 0;
@@ -317,7 +346,7 @@ static int lpa_plan_by_import(mplx_lpa *l, const mplx_waypoint *start, const mpl
 static int lpa_subtree_by_import(mplx_lpa *l, int time_step, const SearchParams &P, const LpaParams &A) {
   int r;
   if ((r = lpa_import_lane(l, true)) != MPLX_OK) return r;
-  mplx_ctx *lane = l->imp;
+  mplx_ctx *lane = l->ln->imp;
   mplx_waypoint start{};
   const double *s = &l->traj_states[(size_t)(l->traj_len - time_step) * 13];
   for (int k = 0; k < 3; k++) { start.pos[k] = s[k]; start.vel[k] = s[3 + k]; start.acc[k] = s[6 + k]; start.jrk[k] = s[9 + k]; }
@@ -337,7 +366,7 @@ static int lpa_subtree_by_import(mplx_lpa *l, int time_step, const SearchParams 
 static int lpa_subtree_by_fresh_plan(mplx_lpa *l, int time_step, const SearchParams &P, const LpaParams &A) {
   int r;
   if ((r = lpa_import_lane(l, false)) != MPLX_OK) return r;
-  mplx_ctx *lane = l->imp;
+  mplx_ctx *lane = l->ln->imp;
   mplx_waypoint start{};
   const double *s = &l->traj_states[(size_t)(l->traj_len - time_step) * 13];
   for (int k = 0; k < 3; k++) { start.pos[k] = s[k]; start.vel[k] = s[3 + k]; start.acc[k] = s[6 + k]; start.jrk[k] = s[9 + k]; }
@@ -349,29 +378,81 @@ static int lpa_subtree_by_fresh_plan(mplx_lpa *l, int time_step, const SearchPar
   return lpa_import_launch(l, P, A, 2, &imp_ms);
 }
 
-// PlannerBase::plan with setLPAstar(true) (map_replanner_node.cpp:141): repairs and re-uses the state space of the
-// previous plan when the goal, the planner set-up and the start (= the current root) are unchanged; otherwise starts one.
-extern "C" int mplx_lpa_plan(mplx_lpa *l, const mplx_waypoint *start, const mplx_waypoint *goal, mplx_result *out) {
-  if (!l || !start || !goal || !out) return lfail(l, MPLX_ERR_ARG, "null argument");
-  mplx_ctx *c = l->ctx;
-  int r = check_ready(c);
-  if (r) return lfail(l, r, "%s", c->err.c_str());
-  if (start->enable_t) return lfail(l, MPLX_ERR_ARG, "enable_t is not supported by the voxel-map environment");
-  if (!control_ok(goal->control)) return lfail(l, MPLX_ERR_ARG, "bad goal control");
-  if (c->yaw) return lfail(l, MPLX_ERR_ARG, "LPA* over yaw-carrying states is not supported (no caller in the reference: map_replanner_node.cpp plans without yaw)");
-  if (c->aux) return lfail(l, MPLX_ERR_ARG, "LPA* with a potential field / search region on the context is not supported (the edge cost would not be a function of the control input)");
-  LCHK(l, hipSetDevice(c->device));
-  if ((r = lpa_ensure(l)) != MPLX_OK) return r;
-  QueryIn in{};
+// what plan() refuses before any device work (null: nothing); *code: the error code
+static const char *lpa_plan_refusal(mplx_ctx *c, const mplx_waypoint *start, const mplx_waypoint *goal, int *code) {
+  *code = check_ready(c);
+  if (*code) return c->err.c_str();
+  *code = MPLX_ERR_ARG;
+  if (start->enable_t) return "enable_t is not supported by the voxel-map environment";
+  if (!control_ok(goal->control)) return "bad goal control";
+  if (c->yaw) return "LPA* over yaw-carrying states is not supported (no caller in the reference: map_replanner_node.cpp plans without yaw)";
+  if (c->aux) return "LPA* with a potential field / search region on the context is not supported (the edge cost would not be a function of the control input)";
+  *code = MPLX_OK;
+  return nullptr;
+}
+// the query of a plan() and the key of its start; true: the plan is FRESH (no space, or the set-up, the goal or the root changed)
+static bool lpa_query(const mplx_lpa *l, const mplx_waypoint *start, const mplx_waypoint *goal, QueryIn &in, int32_t *key) {
+  const mplx_ctx *c = l->ctx;
   mplx_waypoint s = *start;
   s.control = c->cfg.control;
   wp_to_state(s, in.start);
   wp_to_state(*goal, in.goal);
   in.start_t = start->t;
   in.goal_control = goal->control;
-  int32_t key[MAX_KEY] = {};
   const int nk = state_key(c->cfg.control, in.start, key);
-  bool fresh = !l->valid || !lpa_same_setup(l) || !lpa_same_goal(l->goal, *goal) || memcmp(key, l->root_key, sizeof(int32_t) * (size_t)nk) != 0;
+  return !l->valid || !lpa_same_setup(l) || !lpa_same_goal(l->goal, *goal) || memcmp(key, l->root_key, sizeof(int32_t) * (size_t)nk) != 0;
+}
+// what a plan() leaves on the host once l->last_out and l->st hold the launch's QueryOut and LpaState: the result, whether the space
+// stays, the trajectory (`sync`: wait for its copies; a fleet waits once for all its members)
+static int lpa_plan_finish(mplx_lpa *l, bool fresh, const int32_t *key, const mplx_waypoint *goal, mplx_result *out, bool sync) {
+  mplx_ctx *c = l->ctx;
+  fill_result(l->last_out, *out);
+  if (fresh) {  // whatever the outcome, the old space is gone
+    l->valid = false;
+    l->traj_len = 0;
+  }
+  // Pool exhaustion ends the launch in the middle of an expansion (the expanded state is already marked built, its
+  // successors are not all linked): the space is not reusable -- the next plan() starts a fresh one, as after a failed
+  // update (lpa_update).  The result of THIS call (status MPLX_PLAN_POOL_FULL) still says what happened.
+  if (l->last_out.status == MPLX_PLAN_POOL_FULL) {
+    l->valid = false;
+    l->traj_len = 0;
+  } else if (l->st.valid) {
+    l->valid = true;
+    l->cfg = c->cfg;
+    l->U = c->U;
+    l->cfg.U = nullptr;
+    l->goal = *goal;
+    if (fresh) memcpy(l->root_key, key, sizeof(int32_t) * MAX_KEY);
+  }
+  if (l->last_out.status == MPLX_PLAN_OK) {
+    const int len = l->last_out.traj_len;
+    l->traj_len = len;
+    l->traj_nodes.assign((size_t)len + 1, 0);
+    l->traj_actions.assign((size_t)std::max(len, 1), 0);
+    l->traj_states.assign((size_t)(len + 1) * 13, 0.0);
+    if (len > 0) {
+      LCHK(l, hipMemcpyAsync(l->traj_nodes.data(), l->d_traj_nodes, sizeof(int32_t) * (size_t)(len + 1), hipMemcpyDeviceToHost, c->stream));
+      LCHK(l, hipMemcpyAsync(l->traj_actions.data(), l->d_traj_actions, sizeof(int32_t) * (size_t)len, hipMemcpyDeviceToHost, c->stream));
+      LCHK(l, hipMemcpyAsync(l->traj_states.data(), l->d_traj_states, sizeof(double) * (size_t)(len + 1) * 13, hipMemcpyDeviceToHost, c->stream));
+      if (sync) LCHK(l, hipStreamSynchronize(c->stream));
+    }
+  }
+  return MPLX_OK;
+}
+
+// PlannerBase::plan with setLPAstar(true) (map_replanner_node.cpp:141): repairs and re-uses the state space of the
+// previous plan when the goal, the planner set-up and the start (= the current root) are unchanged; otherwise starts one.
+extern "C" int mplx_lpa_plan(mplx_lpa *l, const mplx_waypoint *start, const mplx_waypoint *goal, mplx_result *out) {
+  if (!l || !start || !goal || !out) return lfail(l, MPLX_ERR_ARG, "null argument");
+  mplx_ctx *c = l->ctx;
+  int r;
+  if (const char *why = lpa_plan_refusal(c, start, goal, &r)) return lfail(l, r, "%s", why);
+  LCHK(l, hipSetDevice(c->device));
+  if ((r = lpa_ensure(l)) != MPLX_OK) return r;
+  QueryIn in{};
+  int32_t key[MAX_KEY] = {};
+  const bool fresh = lpa_query(l, start, goal, in, key);
   SearchParams P;
   LpaParams A;
   lpa_params(l, l->cur, P, A);
@@ -408,39 +489,7 @@ extern "C" int mplx_lpa_plan(mplx_lpa *l, const mplx_waypoint *start, const mplx
   LCHK(l, hipMemcpyAsync(&l->last_out, l->d_out, sizeof(QueryOut), hipMemcpyDeviceToHost, c->stream));
   LCHK(l, hipMemcpyAsync(&l->st, A.st, sizeof(LpaState), hipMemcpyDeviceToHost, c->stream));
   LCHK(l, hipStreamSynchronize(c->stream));
-  fill_result(l->last_out, *out);
-  if (fresh) {  // whatever the outcome, the old space is gone
-    l->valid = false;
-    l->traj_len = 0;
-  }
-  // Pool exhaustion ends the launch in the middle of an expansion (the expanded state is already marked built, its
-  // successors are not all linked): the space is not reusable -- the next plan() starts a fresh one, as after a failed
-  // update (lpa_update).  The result of THIS call (status MPLX_PLAN_POOL_FULL) still says what happened.
-  if (l->last_out.status == MPLX_PLAN_POOL_FULL) {
-    l->valid = false;
-    l->traj_len = 0;
-  } else if (l->st.valid) {
-    l->valid = true;
-    l->cfg = c->cfg;
-    l->U = c->U;
-    l->cfg.U = nullptr;
-    l->goal = *goal;
-    if (fresh) memcpy(l->root_key, key, sizeof(key));
-  }
-  if (l->last_out.status == MPLX_PLAN_OK) {
-    const int len = l->last_out.traj_len;
-    l->traj_len = len;
-    l->traj_nodes.assign((size_t)len + 1, 0);
-    l->traj_actions.assign((size_t)std::max(len, 1), 0);
-    l->traj_states.assign((size_t)(len + 1) * 13, 0.0);
-    if (len > 0) {
-      LCHK(l, hipMemcpyAsync(l->traj_nodes.data(), l->d_traj_nodes, sizeof(int32_t) * (size_t)(len + 1), hipMemcpyDeviceToHost, c->stream));
-      LCHK(l, hipMemcpyAsync(l->traj_actions.data(), l->d_traj_actions, sizeof(int32_t) * (size_t)len, hipMemcpyDeviceToHost, c->stream));
-      LCHK(l, hipMemcpyAsync(l->traj_states.data(), l->d_traj_states, sizeof(double) * (size_t)(len + 1) * 13, hipMemcpyDeviceToHost, c->stream));
-      LCHK(l, hipStreamSynchronize(c->stream));
-    }
-  }
-  return MPLX_OK;
+  return lpa_plan_finish(l, fresh, key, goal, out, true);
 }
 
 static int lpa_update(mplx_lpa *l, int mode, int n_cells, const int32_t *cells, uint64_t *n_changed) {
@@ -516,7 +565,7 @@ extern "C" int mplx_lpa_sub_state_space(mplx_lpa *l, int32_t time_step) {
     LCHK(l, hipMemcpyAsync(&ns, A.st, sizeof(LpaState), hipMemcpyDeviceToHost, c->stream));
     LCHK(l, hipStreamSynchronize(c->stream));
     if (!ns.valid) {  // (the new root already satisfies the goal, or the pools ran out: no space is kept -- the next plan() starts one)
-      const bool no_search = l->imp->last_out[0].n_nodes == 0;
+      const bool no_search = l->ln->imp->last_out[0].n_nodes == 0;
       l->valid = false;
       if (no_search) return MPLX_OK;
       return lfail(l, MPLX_ERR_CAPACITY, "LPA* pools exhausted while rebuilding the sub state space (mplx_lpa_set_capacity)");
@@ -681,3 +730,4 @@ extern "C" int mplx_lpa_result_edges(mplx_lpa *l, int32_t *child, int32_t *paren
   *n_out = w;
   return MPLX_OK;
 }
+

@@ -992,6 +992,181 @@ class VoxelMapPlanner:
 # the 2-D lattice is the 3-D path with z frozen -- one layer of voxels whose centre plane is z = 0,
 # control inputs (ux, uy, 0).  Every z term of the polynomial, key, cost and heuristic arithmetic is
 # an exact +0.0, so states, keys, costs and the expansion order equal those of a genuinely 2-D run.
+class _LpaMember(_Lpa):
+    """A fleet's member: an mplx_lpa the fleet owns (borrowed handle; holds the fleet alive)."""
+
+    def __init__(self, fleet_handle, i):
+        self.ctx = fleet_handle.ctx
+        self.lib = fleet_handle.lib
+        self._fleet = fleet_handle
+        self.h = C.c_void_p(self.lib.mplx_lpa_fleet_member(fleet_handle.h, i))
+
+    def __del__(self):
+        self.h = None
+
+
+class _LpaFleetHandle:
+    def __init__(self, ctx, n):
+        self.ctx = ctx
+        self.lib = ctx.lib
+        h = C.c_void_p()
+        code = self.lib.mplx_lpa_fleet_create(ctx.h, n, C.byref(h))
+        if code != _capi.OK:
+            raise MplxError(f"mplx_lpa_fleet_create failed ({code})")
+        self.h = h
+
+    def check(self, code, accept=()):
+        if code != _capi.OK and code not in accept:
+            msg = self.lib.mplx_lpa_fleet_last_error(self.h)
+            raise MplxError(f"mplx error {code}: {msg.decode() if msg else ''}")
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                self.lib.mplx_lpa_fleet_destroy(self.h)
+            self.h = None
+        except Exception:
+            pass
+
+
+class LpaFleet(VoxelMapPlanner):
+    """N LPA* planners (N VoxelMapPlanners with setLPAstar(True)) on one MapUtil and one planner set-up -- N robots that each keep a
+    state space on a shared, changing map -- whose plan() and updateBlockedNodes() / updateClearedNodes() run for all members at once
+    (mplx_lpa_fleet_*): the repairs in ONE launch, one workgroup per member.  Per member every result is what the same sequence of
+    calls on a planner of its own gives.  The planner setters are VoxelMapPlanner's; the per-member getters take the member's index."""
+
+    def __init__(self, map_util, n, verbose=False):
+        super().__init__(verbose)
+        self.setMapUtil(map_util)
+        self._use_lpastar = True
+        self.n = int(n)
+        self._fleet = _LpaFleetHandle(map_util.ctx, self.n)
+        self._members = []
+        for i in range(self.n):  # a view per member: VoxelMapPlanner's getters on the member's handle
+            v = VoxelMapPlanner(verbose)
+            v.map_util_ = map_util
+            v._use_lpastar = True
+            v._lpa = _LpaMember(self._fleet, i)
+            self._members.append(v)
+
+    def setLPAstar(self, use_lpastar):
+        if not use_lpastar:
+            raise MplxError("a fleet's members are LPA* planners")
+
+    def member(self, i):
+        """Member i as a VoxelMapPlanner view (getTraj, lpaStateSpace, getExpandedIds, initialized, reset, setSubStateSpaceMode ...)."""
+        return self._members[i]
+
+    def setCapacity(self, n_slots=0, max_nodes=0, max_edges=0, max_open_log=0, member=None):
+        """Capacities of every member's state space (of one member with member=i); n_slots is the shared context's."""
+        ctx = self._ctx()
+        if member is None:
+            ctx.check(ctx.lib.mplx_set_capacity(ctx.h, n_slots, max_nodes, max_edges, max_open_log))
+            self._fleet.check(ctx.lib.mplx_lpa_fleet_set_capacity(self._fleet.h, max_nodes, max_edges, max_open_log))
+        else:
+            m = self._members[member]._lpa
+            m.check(ctx.lib.mplx_lpa_set_capacity(m.h, max_nodes, max_edges, max_open_log))
+
+    def setRecord(self, cap):
+        super().setRecord(cap)
+        for v in self._members:
+            v._lpa.check(v._lpa.lib.mplx_lpa_set_record(v._lpa.h, int(cap)))
+
+    def plan(self, starts, goals, active=None):
+        """plan(starts[i], goals[i]) of every member (of those with active[i]); returns the list of results (None for an inactive
+        member, whose state space and stored trajectory stay as they are)."""
+        if len(starts) != self.n or len(goals) != self.n:
+            raise MplxError(f"a fleet of {self.n} plans {self.n} queries")
+        if self._U_yaw is not None:
+            raise MplxError("LPA* over yaw-carrying states is not supported")
+        ctx = self._ctx()
+        self._configure(starts[0].control)
+        self._apply_aux()
+        S = (_capi.Waypoint * self.n)(*[w.to_c() for w in starts])
+        G = (_capi.Waypoint * self.n)(*[w.to_c() for w in goals])
+        R = (_capi.Result * self.n)()
+        act = None if active is None else np.ascontiguousarray([1 if a else 0 for a in active], dtype=np.int32)
+        self._fleet.check(ctx.lib.mplx_lpa_fleet_plan(self._fleet.h, S, G, None if act is None else act.ctypes.data, R))
+        out = []
+        for i, v in enumerate(self._members):
+            if act is not None and not act[i]:
+                out.append(None)
+                continue
+            res = _capi.Result.from_buffer_copy(R[i])
+            v._control = starts[0].control
+            v._result, v._results = res, [res]
+            v.traj_cost_ = res.cost
+            out.append(res)
+        self._results = out
+        return out
+
+    def _update_nodes(self, fn, pns):
+        if self._control is None:  # (nothing was planned yet: no member holds a state space)
+            return [0] * self.n
+        self._configure(self._control)
+        c = np.ascontiguousarray(pns, dtype=np.int32).reshape(-1, 3)
+        n = np.zeros(self.n, dtype=np.uint64)
+        # (a member whose conversion ran out of pool is dropped alone: its count reads ~0, the others keep their spaces)
+        self._fleet.check(getattr(self._fleet.lib, fn)(self._fleet.h, c.shape[0], c.ctypes.data, n.ctypes.data), accept=(_capi.ERR_CAPACITY,))
+        return [int(x) for x in n]
+
+    def updateBlockedNodes(self, blocked_pns):
+        """updateBlockedNodes of every member that holds a state space; returns the per-member counts."""
+        return self._update_nodes("mplx_lpa_fleet_update_blocked", blocked_pns)
+
+    def updateClearedNodes(self, cleared_pns):
+        return self._update_nodes("mplx_lpa_fleet_update_cleared", cleared_pns)
+
+    def getSubStateSpace(self, time_steps):
+        """getSubStateSpace(time_steps[i]) of member i (one int: of every member; < 0 leaves the member alone)."""
+        ts = np.full(self.n, int(time_steps), dtype=np.int32) if np.isscalar(time_steps) else np.ascontiguousarray(time_steps, dtype=np.int32)
+        if ts.shape[0] != self.n:
+            raise MplxError(f"a fleet of {self.n} takes {self.n} time steps")
+        if self._control is None:
+            return
+        self._configure(self._control)
+        self._fleet.check(self._fleet.lib.mplx_lpa_fleet_sub_state_space(self._fleet.h, ts.ctypes.data))
+
+    def getTraj(self, i=0):
+        return self._members[i].getTraj()
+
+    def getResult(self, i=0):
+        return self._members[i].getResult()
+
+    def lpaStateSpace(self, i=0):
+        return self._members[i].lpaStateSpace()
+
+    def getExpandedIds(self, i=0):
+        return self._members[i].getExpandedIds()
+
+    def initialized(self, i=None):
+        """PlannerBase::initialized() of member i (None: the list over the members)."""
+        if i is None:
+            return [v.initialized() for v in self._members]
+        return self._members[i].initialized()
+
+    def reset(self, i=None):
+        for v in (self._members if i is None else [self._members[i]]):
+            v.reset()
+
+    def setSubStateSpaceMode(self, mode):
+        for v in self._members:
+            v.setSubStateSpaceMode(mode)
+
+    def stats(self):
+        """The last plan(): [members repaired in the fleet launch, search launches that took (1 or 0), members planned afresh,
+        members skipped (inactive)]."""
+        st = (C.c_uint32 * 4)()
+        self._fleet.check(self._fleet.lib.mplx_lpa_fleet_stats(self._fleet.h, st))
+        return [int(x) for x in st]
+
+    def lastKernelMs(self):
+        """(repair_ms, fresh_ms) of the last plan(): the fleet launch; the sum over the members planned afresh."""
+        a, b = C.c_float(), C.c_float()
+        self._fleet.check(self._fleet.lib.mplx_lpa_fleet_last_kernel_ms(self._fleet.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+
 class PlanStream:
     """Host mirror of mplx_stream: several query batches in flight on one map replica.  While the longest queries of
     batch n still run (a query is a serial pop chain on one compute unit), the workgroups of batch n + 1 take the rest
