@@ -504,6 +504,39 @@ int mplx_plpa_result_expanded(mplx_plpa *l, uint32_t cap, int32_t *ids, uint32_t
  * order: child, parent, action, blocked */
 int mplx_plpa_result_nodes(mplx_plpa *l, uint64_t cap, double *states, double *g, double *rhs, double *h, int32_t *closed, int32_t *opened, int32_t *built);
 int mplx_plpa_result_entries(mplx_plpa *l, uint64_t cap, int32_t *child, int32_t *parent, int32_t *action, int32_t *blocked);
+/* ---- Fleets of them: N mplx_plpa planners on ONE mplx_poly handle (its lattice, limits, worlds and obstacles), each bound to a world
+ *      index (members may share a world), whose plan(), updateNodes() and getSubStateSpace() run for all members at once.  A member is
+ *      an ordinary mplx_plpa -- every mplx_plpa_* getter works on it, and so does mplx_plpa_plan on a single member -- owned by the fleet
+ *      (mplx_plpa_destroy ignores it).  Per member every result is what the same sequence of single-handle calls gives.  A fresh plan
+ *      runs on the same kernel as a repair, so fresh plans, repairs and re-roots of different members share ONE launch. ---- */
+typedef struct mplx_plpa_fleet mplx_plpa_fleet;
+int mplx_plpa_fleet_create(mplx_poly *p, int32_t n, const int32_t *world_of, mplx_plpa_fleet **out);  /* no device work; destroy it before p */
+void mplx_plpa_fleet_destroy(mplx_plpa_fleet *f);
+const char *mplx_plpa_fleet_last_error(const mplx_plpa_fleet *f);
+int mplx_plpa_fleet_size(const mplx_plpa_fleet *f);
+mplx_plpa *mplx_plpa_fleet_member(mplx_plpa_fleet *f, int32_t i);  /* borrowed */
+int mplx_plpa_fleet_set_capacity(mplx_plpa_fleet *f, uint64_t nodes, uint64_t edges, uint64_t open_log);  /* per member (0 = keep) */
+int mplx_plpa_fleet_set_world(mplx_plpa_fleet *f, int32_t i, int32_t world);
+/* plan() of every member i with active[i] != 0 (NULL: all) from starts[i] to goals[i] (n x 9: pos2 vel2 acc2 jrk2 t) in the member's
+ * world; out: n results (zeroed for an inactive member, whose space and stored trajectory stay).  Decided per member as mplx_plpa_plan
+ * decides; all active members, the fresh and the repairing side by side, go into one launch, one workgroup each.  A per-member outcome
+ * (MPLX_PLAN_POOL_FULL, a start outside the map, a start at the goal, the cap reached) ends that member only; what mplx_plpa_plan
+ * refuses (control kind, lattice width, a world index out of range) is refused for the whole call before any launch.  A launch
+ * aborted by the deadline invalidates every member that was in it (MPLX_ERR_TIMEOUT). */
+int mplx_plpa_fleet_plan(mplx_plpa_fleet *f, const double *starts, const double *goals, const int32_t *active, double eps, double tol_pos, double tol_vel,
+                         int32_t max_expand, int32_t heur_ignore_dynamics, mplx_result *out);
+/* mplx_plpa_update_nodes of every member that holds a state space, in one launch.  n_blocked / n_cleared (n entries each, or NULL):
+ * per member, 0 for a member without a space; mplx_plpa_changed on a member answers as after a single call.  A member that met a
+ * hyperplane equation of unsupported degree is invalidated alone (MPLX_ERR_ARG). */
+int mplx_plpa_fleet_update_nodes(mplx_plpa_fleet *f, uint64_t *n_blocked, uint64_t *n_cleared);
+/* mplx_plpa_sub_state_space(member i, time_step[i]) for all members asked in one launch; time_step[i] < 0 leaves the member alone.
+ * The members asked must have been planned under one set-up (eps, tolerances, cap), as a fleet plan leaves them. */
+int mplx_plpa_fleet_sub_state_space(mplx_plpa_fleet *f, const int32_t *time_step);
+/* the last mplx_plpa_fleet_plan / _sub_state_space: [0] members repaired, [1] search launches that took (1, or 0 when no member ran),
+ * [2] members planned afresh, [3] members skipped (inactive / not asked) */
+int mplx_plpa_fleet_stats(const mplx_plpa_fleet *f, uint32_t stats[4]);
+/* kernel time of the last fleet search launch and of the last fleet updateNodes launch */
+int mplx_plpa_fleet_last_kernel_ms(const mplx_plpa_fleet *f, float *plan_ms, float *update_ms);
 int mplx_poly_last_helpers(const mplx_poly *p); /* helpers per leader of the last launch */
 /* Launch guard of the moving-obstacle search: see mplx_set_deadline (a tick that outlives it returns MPLX_ERR_TIMEOUT). */
 int mplx_poly_set_deadline(mplx_poly *p, double seconds);

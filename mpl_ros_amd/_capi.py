@@ -76,6 +76,9 @@ EXPORTS = [
     "mplx_poly_set_record", "mplx_poly_result_expanded", "mplx_poly_last_kernel_ms", "mplx_poly_result_cycles", "mplx_poly_set_helpers", "mplx_poly_last_helpers", "mplx_poly_set_deadline", "mplx_plpa_create", "mplx_plpa_destroy", "mplx_plpa_last_error", "mplx_plpa_set_capacity", "mplx_plpa_initialized", "mplx_plpa_reset",
     "mplx_plpa_plan", "mplx_plpa_update_nodes", "mplx_plpa_changed", "mplx_plpa_sub_state_space", "mplx_plpa_traj_len", "mplx_plpa_result_traj", "mplx_plpa_last_kernel_ms", "mplx_plpa_result_cycles",
     "mplx_plpa_counts", "mplx_plpa_result_expanded", "mplx_plpa_result_nodes", "mplx_plpa_result_entries",
+    "mplx_plpa_fleet_create", "mplx_plpa_fleet_destroy", "mplx_plpa_fleet_last_error", "mplx_plpa_fleet_size", "mplx_plpa_fleet_member", "mplx_plpa_fleet_set_capacity",
+    "mplx_plpa_fleet_set_world", "mplx_plpa_fleet_plan", "mplx_plpa_fleet_update_nodes", "mplx_plpa_fleet_sub_state_space", "mplx_plpa_fleet_stats",
+    "mplx_plpa_fleet_last_kernel_ms",
     "mplx_traj_solve", "mplx_traj_sample", "mplx_traj_effort",
     "mplx_plan_batch_submit", "mplx_plan_batch_wait", "mplx_plan_batch_done", "mplx_set_helper_limit", "mplx_release_pools",
     "mplx_set_deadline", "mplx_set_pool_recycling", "mplx_debug_hang_next_launch", "mplx_debug_query_records",
@@ -268,6 +271,21 @@ def load():
     L.mplx_plpa_result_expanded.argtypes = [P, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     L.mplx_plpa_result_nodes.argtypes = [P, C.c_uint64] + [C.c_void_p] * 7
     L.mplx_plpa_result_entries.argtypes = [P, C.c_uint64] + [C.c_void_p] * 4
+    L.mplx_plpa_fleet_create.argtypes = [P, C.c_int32, C.c_void_p, C.POINTER(P)]
+    L.mplx_plpa_fleet_destroy.argtypes = [P]
+    L.mplx_plpa_fleet_destroy.restype = None
+    L.mplx_plpa_fleet_last_error.argtypes = [P]
+    L.mplx_plpa_fleet_last_error.restype = C.c_char_p
+    L.mplx_plpa_fleet_size.argtypes = [P]
+    L.mplx_plpa_fleet_member.argtypes = [P, C.c_int32]
+    L.mplx_plpa_fleet_member.restype = P
+    L.mplx_plpa_fleet_set_capacity.argtypes = [P, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.mplx_plpa_fleet_set_world.argtypes = [P, C.c_int32, C.c_int32]
+    L.mplx_plpa_fleet_plan.argtypes = [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.POINTER(Result)]
+    L.mplx_plpa_fleet_update_nodes.argtypes = [P, C.c_void_p, C.c_void_p]
+    L.mplx_plpa_fleet_sub_state_space.argtypes = [P, C.c_void_p]
+    L.mplx_plpa_fleet_stats.argtypes = [P, C.c_void_p]
+    L.mplx_plpa_fleet_last_kernel_ms.argtypes = [P, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.mplx_plan_batch_submit.argtypes = [P, C.c_int, C.POINTER(Waypoint), C.POINTER(Waypoint)]
     L.mplx_plan_batch_wait.argtypes = [P, C.POINTER(Result)]
     L.mplx_plan_batch_done.argtypes = [P]

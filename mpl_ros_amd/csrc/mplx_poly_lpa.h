@@ -33,7 +33,12 @@ struct PlpaArgs {
   LpaState *st;
   int32_t fresh;        // start a new state space (the host cleared the table)
   int32_t world;        // index into PolyDev::worlds
-  uint32_t *changed;    // (update) edge index | now blocked << 31, appended in no particular order
+  union {
+    uint32_t *changed;  // (update) edge index | now blocked << 31, appended in no particular order
+    // FLEET builds of plpa_plan_kernel / plpa_update_kernel: one descriptor per member (`changed` is the member's own then).  It
+    // shares the word of `changed` so that the struct -- and with it the argument layout of the single-planner kernels -- stays as it was.
+    const struct PlpaMember *members;
+  };
   uint32_t changed_cap;
   uint32_t *counters;   // (update) [0] entries that became blocked, [1] became free, [2] appended to `changed`, [3] unsupported degree met
   double *edge_cost;    // per predecessor entry: calculate_intrinsic_cost of its primitive, written when the entry is (the parent state never changes)
@@ -42,6 +47,42 @@ struct PlpaArgs {
   int32_t trust_entries;  // the entries' blocked bits are those of the world as committed now (a fresh space, or updateNodes ran after the last commit):
                           // a state that is expanded AGAIN reads its successors' outcomes from its entries instead of running get_succ once more
 };
+
+// A fleet is N planners on ONE mplx_poly handle (lattice, limits, worlds, obstacles) whose plans -- fresh ones and repairs side by
+// side -- and whose updateNodes walks run in one launch (mplx_plpa_fleet_*).  What differs between the members comes from this
+// descriptor (device memory, read once per workgroup; the loads are uniform); the environment, eps, the tolerances, max_expand, the
+// heuristic mode, the bucket width and the launch guard are the launch's SearchParams.
+struct PlpaMember {
+  char *node_pool, *edge_pool, *open_pool;
+  unsigned long long *table;
+  unsigned long long table_mask;
+  uint32_t *bkt_head;
+  LpaState *st;
+  const QueryIn *query;
+  QueryOut *out;
+  int32_t *traj_nodes, *traj_actions;
+  double *traj_states;
+  int32_t *rec_ids;
+  double *edge_cost;
+  uint32_t *succ_child, *succ_entry;
+  uint32_t *changed, *counters;
+  uint32_t node_chunks, edge_chunks, open_chunks, cap_rec, changed_cap;
+  int32_t world, fresh, trust_entries;
+};
+__device__ __forceinline__ void plpa_member_args(SearchParams &P, PlpaArgs &A, const PlpaMember &m) {
+  P.node_pool = m.node_pool; P.edge_pool = m.edge_pool; P.open_pool = m.open_pool;
+  P.table = m.table; P.table_mask = m.table_mask;
+  P.bkt_head = m.bkt_head;
+  P.queries = m.query; P.out = m.out;
+  P.traj_nodes = m.traj_nodes; P.traj_actions = m.traj_actions; P.traj_states = m.traj_states;
+  P.rec_ids = m.rec_ids;
+  P.node_chunks = m.node_chunks; P.edge_chunks = m.edge_chunks; P.open_chunks = m.open_chunks; P.cap_rec = m.cap_rec;
+  A.st = m.st; A.fresh = m.fresh; A.world = m.world;
+  A.edge_cost = m.edge_cost; A.succ_child = m.succ_child; A.succ_entry = m.succ_entry;
+  A.trust_entries = m.trust_entries;
+  A.changed_cap = m.changed_cap; A.counters = m.counters;
+  A.changed = m.changed;  // (last: it shares its word with A.members)
+}
 
 // isFree(pr, t) of PolyMapUtil (poly_map_util.h:92-109) for the primitive `cs` that starts at time t_rel (relative to the world's start
 // time): the start point against every obstacle, then collide() per obstacle, in the order the obstacles were added (static, linear,
@@ -108,8 +149,10 @@ __device__ __forceinline__ uint32_t plpa_find(const SearchParams &P, const int32
 }
 
 // ------------------------------------------------------------------ ComputeShortestPath
-template <int CONTROL, bool GEN>
+// FLEET: the plan (fresh or repair) of member blockIdx.x of a fleet (PlpaMember); one workgroup per member, no dependency between them
+template <int CONTROL, bool GEN, bool FLEET = false>
 __global__ __launch_bounds__(64) void plpa_plan_kernel(SearchParams P, PlpaArgs A) {
+  if constexpr (FLEET) plpa_member_args(P, A, A.members[blockIdx.x]);
   constexpr int BLOCK = 64;
   static_assert(CONTROL == CTRL_ACC || CONTROL == CTRL_JRK, "time-keyed states of the moving-obstacle environment");
   constexpr int ns = key_len_c(CONTROL), NK = ns + 1;
@@ -670,8 +713,10 @@ __global__ __launch_bounds__(64) void plpa_plan_kernel(SearchParams P, PlpaArgs 
 // One lane per state: every predecessor entry re-tested against the current obstacles (forward_action + isFree(pr, pred.t)); an
 // entry whose outcome changed flips its EDGE_BLOCKED bit (increaseCost / decreaseCost) and is reported; the look-ahead value of a
 // state whose entries changed is recomputed.  (g values do not change here, so the states are independent of each other.)
-template <int CONTROL, bool GEN>
+// FLEET: the member in blockIdx.y, the grid-stride over blockIdx.x inside it
+template <int CONTROL, bool GEN, bool FLEET = false>
 __global__ __launch_bounds__(64) void plpa_update_kernel(SearchParams P, PlpaArgs A) {
+  if constexpr (FLEET) plpa_member_args(P, A, A.members[blockIdx.y]);
   constexpr int BLOCK = 64;
   constexpr int ns = key_len_c(CONTROL);
   __shared__ Smem<BLOCK> S;

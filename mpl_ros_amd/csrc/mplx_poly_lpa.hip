@@ -17,49 +17,11 @@
 #include <string>
 #include <vector>
 
-#include "mplx_poly_lpa.h"
-#include "mplx_poly_lpa_host.h"
+#include "mplx_poly_lpa_handle.h"
 
 using namespace mplx;
 
 extern "C" const char *mplx_poly_last_error(const mplx_poly *p);
-
-struct mplx_plpa {
-  mplx_poly *poly = nullptr;
-  std::string err;
-  // capacities and pools (flat, private to the handle: chunk tables are the identity)
-  uint64_t cap_nodes = 1 << 18, cap_edges = 1 << 21, cap_log = 1 << 21;
-  bool pools_valid = false;
-  int pool_control = 0;
-  char *node_pool = nullptr, *edge_pool = nullptr, *open_pool = nullptr;
-  unsigned long long *table = nullptr;
-  uint64_t table_slots = 0;
-  uint32_t *bkt_head = nullptr;
-  LpaState *d_st = nullptr;
-  QueryIn *d_in = nullptr;
-  QueryOut *d_out = nullptr;
-  int32_t *d_traj_nodes = nullptr, *d_traj_actions = nullptr, *d_rec = nullptr;
-  double *d_traj_states = nullptr;
-  uint32_t *d_changed = nullptr, *d_counters = nullptr;
-  double *d_edge_cost = nullptr;
-  uint32_t *d_succ_child = nullptr, *d_succ_entry = nullptr;  // per state x control input (null when that would be too large)
-  int succ_n_u = 0;
-  uint64_t synced_epoch = ~0ull;  // mplx_poly commit count the entries' blocked bits were last brought in step with
-  uint32_t cap_rec = 0;
-  // host copies
-  LpaState st{};
-  QueryOut last_out{};
-  bool valid = false;
-  double goal[9] = {0}, eps = 1.0, tol_pos = 0.5, tol_vel = -1.0;
-  int32_t max_expand = -1, heur_ignore_dynamics = 1;
-  int32_t root_key[MAX_KEY + 1] = {0};
-  int traj_len = 0;
-  std::vector<int32_t> traj_nodes, traj_actions;
-  std::vector<double> traj_states;
-  std::vector<uint32_t> changed;
-  float last_ms = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-};
 
 static int lf(mplx_plpa *l, int code, const char *fmt, ...) {
   char buf[768];
@@ -83,15 +45,16 @@ static uint64_t np2(uint64_t v) {
 }
 static void plpa_free(mplx_plpa *l) {
   (void)hipFree(l->node_pool); (void)hipFree(l->edge_pool); (void)hipFree(l->open_pool); (void)hipFree(l->table); (void)hipFree(l->bkt_head);
-  (void)hipFree(l->d_st); (void)hipFree(l->d_in); (void)hipFree(l->d_out); (void)hipFree(l->d_traj_nodes); (void)hipFree(l->d_traj_actions);
-  (void)hipFree(l->d_traj_states); (void)hipFree(l->d_changed); (void)hipFree(l->d_counters); (void)hipFree(l->d_rec); (void)hipFree(l->d_edge_cost); (void)hipFree(l->d_succ_child); (void)hipFree(l->d_succ_entry);
+  if (!l->fleet_st) { (void)hipFree(l->d_st); (void)hipFree(l->d_in); (void)hipFree(l->d_out); (void)hipFree(l->d_counters); }
+  (void)hipFree(l->d_traj_nodes); (void)hipFree(l->d_traj_actions);
+  (void)hipFree(l->d_traj_states); (void)hipFree(l->d_changed); (void)hipFree(l->d_rec); (void)hipFree(l->d_edge_cost); (void)hipFree(l->d_succ_child); (void)hipFree(l->d_succ_entry);
   l->d_edge_cost = nullptr; l->d_succ_child = l->d_succ_entry = nullptr;
   l->node_pool = l->edge_pool = l->open_pool = nullptr;
   l->table = nullptr; l->bkt_head = nullptr; l->d_st = nullptr; l->d_in = nullptr; l->d_out = nullptr;
   l->d_traj_nodes = l->d_traj_actions = l->d_rec = nullptr; l->d_traj_states = nullptr; l->d_changed = l->d_counters = nullptr;
   l->pools_valid = false;
 }
-static int plpa_ensure(mplx_plpa *l, int control, int n_u) {
+int plpa_ensure(mplx_plpa *l, int control, int n_u) {
   if (l->pools_valid && l->pool_control == control && l->succ_n_u == n_u) return MPLX_OK;
   plpa_free(l);
   l->valid = false;
@@ -107,14 +70,18 @@ static int plpa_ensure(mplx_plpa *l, int control, int n_u) {
   LH(l, hipMalloc((void **)&l->table, (size_t)l->table_slots * sizeof(unsigned long long)));
   LH(l, hipMalloc((void **)&l->bkt_head, sizeof(uint32_t) * 2 * NB * NSUB));
   LH(l, hipMemset(l->bkt_head, 0xFF, sizeof(uint32_t) * 2 * NB * NSUB));
-  LH(l, hipMalloc((void **)&l->d_st, sizeof(LpaState)));
-  LH(l, hipMalloc((void **)&l->d_in, sizeof(QueryIn)));
-  LH(l, hipMalloc((void **)&l->d_out, sizeof(QueryOut)));
+  if (l->fleet_st) {
+    l->d_st = l->fleet_st; l->d_in = l->fleet_in; l->d_out = l->fleet_out; l->d_counters = l->fleet_counters;
+  } else {
+    LH(l, hipMalloc((void **)&l->d_st, sizeof(LpaState)));
+    LH(l, hipMalloc((void **)&l->d_in, sizeof(QueryIn)));
+    LH(l, hipMalloc((void **)&l->d_out, sizeof(QueryOut)));
+    LH(l, hipMalloc((void **)&l->d_counters, sizeof(uint32_t) * 4));
+  }
   LH(l, hipMalloc((void **)&l->d_traj_nodes, sizeof(int32_t) * (MAX_TRAJ + 1)));
   LH(l, hipMalloc((void **)&l->d_traj_actions, sizeof(int32_t) * MAX_TRAJ));
   LH(l, hipMalloc((void **)&l->d_traj_states, sizeof(double) * (MAX_TRAJ + 1) * 13));
   LH(l, hipMalloc((void **)&l->d_changed, sizeof(uint32_t) * (size_t)(ech << EDGE_CH_LOG)));
-  LH(l, hipMalloc((void **)&l->d_counters, sizeof(uint32_t) * 4));
   LH(l, hipMalloc((void **)&l->d_edge_cost, sizeof(double) * (size_t)(ech << EDGE_CH_LOG)));
   l->succ_n_u = n_u;
   if ((nch << NODE_CH_LOG) * (uint64_t)n_u * 8ull <= (4ull << 30)) {  // (beyond 4 GB the re-expansion shortcut is off: get_succ runs again)
@@ -127,7 +94,7 @@ static int plpa_ensure(mplx_plpa *l, int control, int n_u) {
   l->pools_valid = true;
   return MPLX_OK;
 }
-static void plpa_params(const mplx_plpa *l, const mplx_poly_view &v, SearchParams &P) {
+void plpa_params(const mplx_plpa *l, const mplx_poly_view &v, SearchParams &P) {
   P = SearchParams{};
   P.control = v.dev.control; P.n_u = v.dev.n_u;
   P.ns = state_len(v.dev.control); P.nk = state_len(v.dev.control);
@@ -161,26 +128,33 @@ static void launch_update(int control, int grid, hipStream_t s, const SearchPara
   if (control == CTRL_ACC) hipLaunchKernelGGL((plpa_update_kernel<CTRL_ACC, GEN>), dim3(grid), dim3(64), 0, s, P, A);
   else hipLaunchKernelGGL((plpa_update_kernel<CTRL_JRK, GEN>), dim3(grid), dim3(64), 0, s, P, A);
 }
-// wait for the stream with the handle's launch deadline (opt-in, counted from `t0`): past it the abort word of the planner context's
-// guard block is raised, which plpa_plan_kernel polls
-static int plpa_wait(mplx_plpa *l, const mplx_poly_view &v, std::chrono::steady_clock::time_point t0, const char *what) {
+static int sf(std::string *err, int code, const char *fmt, ...) {
+  char buf[768];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  if (err) *err = buf;
+  return code;
+}
+int plpa_wait(std::string *err, const mplx_poly_view &v, std::chrono::steady_clock::time_point t0, const char *what) {
   using clk = std::chrono::steady_clock;
   bool aborted = false;
   for (;;) {
     const hipError_t e = hipStreamQuery(v.stream);
     if (e == hipSuccess) break;
-    if (e != hipErrorNotReady) return lf(l, MPLX_ERR_HIP, "hipStreamQuery failed while waiting for %s: %s", what, hipGetErrorString(e));
+    if (e != hipErrorNotReady) return sf(err, MPLX_ERR_HIP, "hipStreamQuery failed while waiting for %s: %s", what, hipGetErrorString(e));
     const double el = std::chrono::duration<double>(clk::now() - t0).count();
     if (v.deadline_s > 0 && !aborted && el > v.deadline_s && v.guard) {
       __atomic_store_n(&v.guard->abort, 1u, __ATOMIC_SEQ_CST);
       aborted = true;
     }
-    if (aborted && el > v.deadline_s + 10.0) return lf(l, MPLX_ERR_TIMEOUT, "%s did not end within %.1f s of its launch and did not answer the abort word", what, v.deadline_s);
+    if (aborted && el > v.deadline_s + 10.0) return sf(err, MPLX_ERR_TIMEOUT, "%s did not end within %.1f s of its launch and did not answer the abort word", what, v.deadline_s);
     usleep(el < 0.05 ? 50 : 250);
   }
   if (aborted) {
     __atomic_store_n(&v.guard->abort, 0u, __ATOMIC_SEQ_CST);
-    return lf(l, MPLX_ERR_TIMEOUT, "%s did not end within %.1f s of its launch and was aborted (results of the launch are void)", what, v.deadline_s);
+    return sf(err, MPLX_ERR_TIMEOUT, "%s did not end within %.1f s of its launch and was aborted (results of the launch are void)", what, v.deadline_s);
   }
   return MPLX_OK;
 }
@@ -193,7 +167,7 @@ extern "C" int mplx_plpa_create(mplx_poly *poly, mplx_plpa **out) {
   return MPLX_OK;
 }
 extern "C" void mplx_plpa_destroy(mplx_plpa *l) {
-  if (!l) return;
+  if (!l || l->in_fleet) return;
   plpa_free(l);
   if (l->ev0) (void)hipEventDestroy(l->ev0);
   if (l->ev1) (void)hipEventDestroy(l->ev1);
@@ -216,11 +190,16 @@ extern "C" int mplx_plpa_reset(mplx_plpa *l) {
   return MPLX_OK;
 }
 
+int plpa_poly_view(mplx_poly *poly, std::string *err, mplx_poly_view &v) {
+  const int r = mplx_poly_internal_view(poly, &v);
+  if (r != MPLX_OK) return sf(err, r, "%s", mplx_poly_last_error(poly));
+  if (v.dev.control != CTRL_ACC && v.dev.control != CTRL_JRK) return sf(err, MPLX_ERR_ARG, "the moving-obstacle LPA* runs ACC or JRK states");
+  if (v.dev.n_u > POLY_MAX_U) return sf(err, MPLX_ERR_ARG, "at most %d control inputs", POLY_MAX_U);
+  return MPLX_OK;
+}
 static int plpa_view(mplx_plpa *l, int32_t world, mplx_poly_view &v) {
-  const int r = mplx_poly_internal_view(l->poly, &v);
-  if (r != MPLX_OK) return lf(l, r, "%s", mplx_poly_last_error(l->poly));
-  if (v.dev.control != CTRL_ACC && v.dev.control != CTRL_JRK) return lf(l, MPLX_ERR_ARG, "the moving-obstacle LPA* runs ACC or JRK states");
-  if (v.dev.n_u > POLY_MAX_U) return lf(l, MPLX_ERR_ARG, "at most %d control inputs", POLY_MAX_U);
+  const int r = plpa_poly_view(l->poly, &l->err, v);
+  if (r) return r;
   if (world < 0 || world >= v.n_worlds) return lf(l, MPLX_ERR_ARG, "world index out of range");
   return MPLX_OK;
 }
@@ -232,55 +211,33 @@ static void key_of(int control, const double *s9, int32_t *key) {
   key[n] = (int32_t)round(s9[8] / 0.1);
 }
 
-// PlannerBase::plan with setLPAstar(true) (poly_map_replanner_node.cpp:141): repairs and re-uses the state space of the previous plan when
-// the goal and the start (= the current root) are unchanged (L6); otherwise starts one.  start / goal: pos2 vel2 acc2 jrk2 t.
-static int plpa_plan_impl(mplx_plpa *l, int32_t world, const double *start, const double *goal, bool force_fresh, mplx_result *out) {
-  mplx_poly_view v;
-  int r = plpa_view(l, world, v);
-  if (r) return r;
-  LH(l, hipSetDevice(v.device));
-  const int control = v.dev.control;
-  if ((r = plpa_ensure(l, control, v.dev.n_u)) != MPLX_OK) return r;
-  if (!l->ev0) { LH(l, hipEventCreate(&l->ev0)); LH(l, hipEventCreate(&l->ev1)); }
-  QueryIn in{};
+void plpa_setup(mplx_plpa *l, double eps, double tol_pos, double tol_vel, int32_t max_expand, int32_t heur_ignore_dynamics) {
+  if (l->valid && (l->eps != eps || l->tol_pos != tol_pos || l->tol_vel != tol_vel || l->heur_ignore_dynamics != heur_ignore_dynamics)) l->valid = false;
+  l->eps = eps; l->tol_pos = tol_pos; l->tol_vel = tol_vel; l->max_expand = max_expand; l->heur_ignore_dynamics = heur_ignore_dynamics;
+}
+void plpa_query(const mplx_plpa *l, int control, const double *start, const double *goal, bool force_fresh, PlpaQuery &q) {
+  QueryIn &in = q.in;
+  in = QueryIn{};
   in.start.p[0] = start[0]; in.start.p[1] = start[1]; in.start.v[0] = start[2]; in.start.v[1] = start[3];
   in.goal.p[0] = goal[0]; in.goal.p[1] = goal[1]; in.goal.v[0] = goal[2]; in.goal.v[1] = goal[3];
   if (control == CTRL_JRK) { in.start.a[0] = start[4]; in.start.a[1] = start[5]; in.goal.a[0] = goal[4]; in.goal.a[1] = goal[5]; }
   in.start_t = start[8];
   in.goal_control = control;
-  int32_t key[MAX_KEY + 1] = {0};
-  key_of(control, start, key);
+  memset(q.key, 0, sizeof(q.key));
+  key_of(control, start, q.key);
   bool same_goal = true;
   for (int i = 0; i < 8; i++) same_goal = same_goal && l->goal[i] == goal[i];
-  const bool fresh = force_fresh || !l->valid || !same_goal || memcmp(key, l->root_key, sizeof(key)) != 0;
-  SearchParams P;
-  plpa_params(l, v, P);
-  PlpaArgs A{};
+  q.fresh = force_fresh || !l->valid || !same_goal || memcmp(q.key, l->root_key, sizeof(q.key)) != 0;
+}
+void plpa_plan_args(mplx_plpa *l, const mplx_poly_view &v, int32_t world, bool fresh, PlpaArgs &A) {
+  A = PlpaArgs{};
   A.st = l->d_st; A.fresh = fresh ? 1 : 0; A.world = world; A.edge_cost = l->d_edge_cost;
   A.succ_child = l->d_succ_child; A.succ_entry = l->d_succ_entry;
   // the entries are in step with the committed world when the space is new, or when updateNodes ran after the last commit
   if (fresh) l->synced_epoch = v.commit_epoch;
   A.trust_entries = (l->synced_epoch == v.commit_epoch && getenv("MPLX_PLPA_NO_REUSE") == nullptr) ? 1 : 0;
-  hipStream_t s = v.stream;
-  LH(l, hipMemcpyAsync(l->d_in, &in, sizeof(QueryIn), hipMemcpyHostToDevice, s));
-  if (fresh) {
-    LH(l, hipMemsetAsync(l->table, 0xFF, (size_t)l->table_slots * sizeof(unsigned long long), s));
-    LH(l, hipMemsetAsync(l->d_st, 0, sizeof(LpaState), s));
-  }
-  if (v.guard) memset(v.guard, 0, sizeof(GuardBlock));
-  const auto t0 = std::chrono::steady_clock::now();
-  LH(l, hipEventRecord(l->ev0, s));
-  if (v.general) launch_plan<true>(control, s, P, A); else launch_plan<false>(control, s, P, A);
-  LH(l, hipGetLastError());
-  LH(l, hipEventRecord(l->ev1, s));
-  if ((r = plpa_wait(l, v, t0, "the moving-obstacle LPA* launch")) != MPLX_OK) {
-    l->valid = false;
-    return r;
-  }
-  LH(l, hipMemcpyAsync(&l->last_out, l->d_out, sizeof(QueryOut), hipMemcpyDeviceToHost, s));
-  LH(l, hipMemcpyAsync(&l->st, l->d_st, sizeof(LpaState), hipMemcpyDeviceToHost, s));
-  LH(l, hipStreamSynchronize(s));
-  LH(l, hipEventElapsedTime(&l->last_ms, l->ev0, l->ev1));
+}
+int plpa_plan_finish(mplx_plpa *l, const PlpaQuery &q, const double *goal, mplx_result *out, hipStream_t s) {
   const QueryOut &o = l->last_out;
   if (out) {
     memset(out, 0, sizeof(*out));
@@ -296,8 +253,8 @@ static int plpa_plan_impl(mplx_plpa *l, int32_t world, const double *start, cons
   } else if (l->st.valid) {
     l->valid = true;
     for (int i = 0; i < 9; i++) l->goal[i] = goal[i];
-    if (fresh) memcpy(l->root_key, key, sizeof(key));
-  } else if (fresh) {
+    if (q.fresh) memcpy(l->root_key, q.key, sizeof(q.key));
+  } else if (q.fresh) {
     l->valid = false;  // (the start already satisfies the goal, or lies outside the map: no state space was built)
     for (int i = 0; i < 9; i++) l->goal[i] = goal[i];
   }
@@ -308,20 +265,90 @@ static int plpa_plan_impl(mplx_plpa *l, int32_t world, const double *start, cons
     l->traj_nodes.assign((size_t)len + 1, 0);
     l->traj_actions.assign((size_t)len, 0);
     l->traj_states.assign((size_t)(len + 1) * 13, 0.0);
-    LH(l, hipMemcpy(l->traj_nodes.data(), l->d_traj_nodes, sizeof(int32_t) * (size_t)(len + 1), hipMemcpyDeviceToHost));
-    LH(l, hipMemcpy(l->traj_actions.data(), l->d_traj_actions, sizeof(int32_t) * (size_t)len, hipMemcpyDeviceToHost));
-    LH(l, hipMemcpy(l->traj_states.data(), l->d_traj_states, sizeof(double) * (size_t)(len + 1) * 13, hipMemcpyDeviceToHost));
+    if (s) {
+      LH(l, hipMemcpyAsync(l->traj_nodes.data(), l->d_traj_nodes, sizeof(int32_t) * (size_t)(len + 1), hipMemcpyDeviceToHost, s));
+      LH(l, hipMemcpyAsync(l->traj_actions.data(), l->d_traj_actions, sizeof(int32_t) * (size_t)len, hipMemcpyDeviceToHost, s));
+      LH(l, hipMemcpyAsync(l->traj_states.data(), l->d_traj_states, sizeof(double) * (size_t)(len + 1) * 13, hipMemcpyDeviceToHost, s));
+    } else {
+      LH(l, hipMemcpy(l->traj_nodes.data(), l->d_traj_nodes, sizeof(int32_t) * (size_t)(len + 1), hipMemcpyDeviceToHost));
+      LH(l, hipMemcpy(l->traj_actions.data(), l->d_traj_actions, sizeof(int32_t) * (size_t)len, hipMemcpyDeviceToHost));
+      LH(l, hipMemcpy(l->traj_states.data(), l->d_traj_states, sizeof(double) * (size_t)(len + 1) * 13, hipMemcpyDeviceToHost));
+    }
   }
   return MPLX_OK;
+}
+
+// PlannerBase::plan with setLPAstar(true) (poly_map_replanner_node.cpp:141): repairs and re-uses the state space of the previous plan when
+// the goal and the start (= the current root) are unchanged (L6); otherwise starts one.  start / goal: pos2 vel2 acc2 jrk2 t.
+static int plpa_plan_impl(mplx_plpa *l, int32_t world, const double *start, const double *goal, bool force_fresh, mplx_result *out) {
+  mplx_poly_view v;
+  int r = plpa_view(l, world, v);
+  if (r) return r;
+  LH(l, hipSetDevice(v.device));
+  const int control = v.dev.control;
+  if ((r = plpa_ensure(l, control, v.dev.n_u)) != MPLX_OK) return r;
+  if (!l->ev0) { LH(l, hipEventCreate(&l->ev0)); LH(l, hipEventCreate(&l->ev1)); }
+  PlpaQuery q;
+  plpa_query(l, control, start, goal, force_fresh, q);
+  const bool fresh = q.fresh;
+  SearchParams P;
+  plpa_params(l, v, P);
+  PlpaArgs A;
+  plpa_plan_args(l, v, world, fresh, A);
+  hipStream_t s = v.stream;
+  LH(l, hipMemcpyAsync(l->d_in, &q.in, sizeof(QueryIn), hipMemcpyHostToDevice, s));
+  if (fresh) {
+    LH(l, hipMemsetAsync(l->table, 0xFF, (size_t)l->table_slots * sizeof(unsigned long long), s));
+    LH(l, hipMemsetAsync(l->d_st, 0, sizeof(LpaState), s));
+  }
+  if (v.guard) memset(v.guard, 0, sizeof(GuardBlock));
+  const auto t0 = std::chrono::steady_clock::now();
+  LH(l, hipEventRecord(l->ev0, s));
+  if (v.general) launch_plan<true>(control, s, P, A); else launch_plan<false>(control, s, P, A);
+  LH(l, hipGetLastError());
+  LH(l, hipEventRecord(l->ev1, s));
+  if ((r = plpa_wait(&l->err, v, t0, "the moving-obstacle LPA* launch")) != MPLX_OK) {
+    l->valid = false;
+    return r;
+  }
+  LH(l, hipMemcpyAsync(&l->last_out, l->d_out, sizeof(QueryOut), hipMemcpyDeviceToHost, s));
+  LH(l, hipMemcpyAsync(&l->st, l->d_st, sizeof(LpaState), hipMemcpyDeviceToHost, s));
+  LH(l, hipStreamSynchronize(s));
+  LH(l, hipEventElapsedTime(&l->last_ms, l->ev0, l->ev1));
+  return plpa_plan_finish(l, q, goal, out, nullptr);
 }
 extern "C" int mplx_plpa_plan(mplx_plpa *l, int32_t world, const double *start, const double *goal, double eps, double tol_pos, double tol_vel, int32_t max_expand,
                               int32_t heur_ignore_dynamics, mplx_result *out) {
   if (!l || !start || !goal || !out) return lf(l, MPLX_ERR_ARG, "null argument");
-  if (l->valid && (l->eps != eps || l->tol_pos != tol_pos || l->tol_vel != tol_vel || l->heur_ignore_dynamics != heur_ignore_dynamics)) l->valid = false;
-  l->eps = eps; l->tol_pos = tol_pos; l->tol_vel = tol_vel; l->max_expand = max_expand; l->heur_ignore_dynamics = heur_ignore_dynamics;
+  plpa_setup(l, eps, tol_pos, tol_vel, max_expand, heur_ignore_dynamics);
   return plpa_plan_impl(l, world, start, goal, false, out);
 }
 
+void plpa_update_args(const mplx_plpa *l, int32_t world, const SearchParams &P, PlpaArgs &A) {
+  A = PlpaArgs{};
+  A.st = l->d_st; A.world = world; A.changed = l->d_changed; A.counters = l->d_counters; A.edge_cost = l->d_edge_cost;
+  A.succ_child = l->d_succ_child; A.succ_entry = l->d_succ_entry;
+  A.changed_cap = (uint32_t)std::min<uint64_t>((uint64_t)P.edge_chunks << EDGE_CH_LOG, 0xFFFFFFF0ull);
+}
+int plpa_update_grid(const mplx_plpa *l) { return (int)std::min<uint64_t>(1024, (l->st.n_nodes + 63) / 64 + 1); }
+void plpa_changed_sort(mplx_plpa *l) {
+  std::sort(l->changed.begin(), l->changed.end(), [](uint32_t a, uint32_t b) { return (a & 0x7FFFFFFFu) < (b & 0x7FFFFFFFu); });
+}
+int plpa_update_finish(mplx_plpa *l, const uint32_t ctr[4], uint32_t changed_cap, uint64_t commit_epoch, uint64_t *n_blocked, uint64_t *n_cleared, hipStream_t s) {
+  if (ctr[3]) { l->valid = false; return lf(l, MPLX_ERR_ARG, "internal: a hyperplane equation of unsupported degree was met"); }
+  l->synced_epoch = commit_epoch;  // every entry has just been re-tested against the world as committed now
+  const uint32_t n = std::min(ctr[2], changed_cap);
+  l->changed.resize(n);
+  if (s) {
+    if (n) LH(l, hipMemcpyAsync(l->changed.data(), l->d_changed, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+  } else {
+    if (n) LH(l, hipMemcpy(l->changed.data(), l->d_changed, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+    plpa_changed_sort(l);
+  }
+  if (n_blocked) *n_blocked = ctr[0];
+  if (n_cleared) *n_cleared = ctr[1];
+  return MPLX_OK;
+}
 // PolyMapPlanner::updateNodes (poly_map_planner.h:61-93), after the world's obstacles / start time were committed again
 extern "C" int mplx_plpa_update_nodes(mplx_plpa *l, int32_t world, uint64_t *n_blocked, uint64_t *n_cleared) {
   if (!l) return MPLX_ERR_ARG;
@@ -336,27 +363,17 @@ extern "C" int mplx_plpa_update_nodes(mplx_plpa *l, int32_t world, uint64_t *n_b
   LH(l, hipSetDevice(v.device));
   SearchParams P;
   plpa_params(l, v, P);
-  PlpaArgs A{};
-  A.st = l->d_st; A.world = world; A.changed = l->d_changed; A.counters = l->d_counters; A.edge_cost = l->d_edge_cost;
-  A.succ_child = l->d_succ_child; A.succ_entry = l->d_succ_entry;
-  A.changed_cap = (uint32_t)std::min<uint64_t>((uint64_t)P.edge_chunks << EDGE_CH_LOG, 0xFFFFFFF0ull);
+  PlpaArgs A;
+  plpa_update_args(l, world, P, A);
   hipStream_t s = v.stream;
   LH(l, hipMemsetAsync(l->d_counters, 0, sizeof(uint32_t) * 4, s));
-  const int grid = (int)std::min<uint64_t>(1024, (l->st.n_nodes + 63) / 64 + 1);
+  const int grid = plpa_update_grid(l);
   if (v.general) launch_update<true>(v.dev.control, grid, s, P, A); else launch_update<false>(v.dev.control, grid, s, P, A);
   LH(l, hipGetLastError());
   uint32_t ctr[4] = {0, 0, 0, 0};
   LH(l, hipMemcpyAsync(ctr, l->d_counters, sizeof(ctr), hipMemcpyDeviceToHost, s));
   LH(l, hipStreamSynchronize(s));
-  if (ctr[3]) { l->valid = false; return lf(l, MPLX_ERR_ARG, "internal: a hyperplane equation of unsupported degree was met"); }
-  l->synced_epoch = v.commit_epoch;  // every entry has just been re-tested against the world as committed now
-  const uint32_t n = std::min(ctr[2], A.changed_cap);
-  l->changed.resize(n);
-  if (n) LH(l, hipMemcpy(l->changed.data(), l->d_changed, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-  std::sort(l->changed.begin(), l->changed.end(), [](uint32_t a, uint32_t b) { return (a & 0x7FFFFFFFu) < (b & 0x7FFFFFFFu); });
-  if (n_blocked) *n_blocked = ctr[0];
-  if (n_cleared) *n_cleared = ctr[1];
-  return MPLX_OK;
+  return plpa_update_finish(l, ctr, A.changed_cap, v.commit_epoch, n_blocked, n_cleared, nullptr);
 }
 // the entries updateNodes changed, by entry number: what getBlockedPrimitives / getClearedPrimitives are built from (entry -> parent state
 // and action: mplx_plpa_result_entries / _nodes)

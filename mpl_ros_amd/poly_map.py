@@ -248,6 +248,11 @@ class PolyTeam:
         """A PolyLpa on this team's worlds: the LPA* planner of poly_map_replanner_node.cpp (setLPAstar(true), updateNodes, getSubStateSpace)."""
         return PolyLpa(self)
 
+    def lpa_fleet(self, world_of):
+        """A PolyLpaFleet on this team's worlds: member i is a PolyLpa bound to world world_of[i]; plan / update_nodes /
+        sub_state_space run for all members in one launch."""
+        return PolyLpaFleet(self, world_of)
+
     def last_kernel_ms(self):
         ms = C.c_float()
         self.check(self.lib.mplx_poly_last_kernel_ms(self.h, C.byref(ms)))
@@ -364,8 +369,14 @@ class PolyLpa:
     moving-obstacle environment of ONE world of a PolyTeam (mplx_plpa_*).  The flow of replanCallback / plan() there:
     team.set_worlds(...) (setLinearObstacles, setStartTime) -> update_nodes() -> plan(start, goal) -> sub_state_space(1)."""
 
-    def __init__(self, team, world=0):
+    def __init__(self, team, world=0, handle=None):
+        """handle: a borrowed mplx_plpa (a fleet's member, PolyLpaFleet.member): a view that does not own it"""
         self.team, self.lib, self.world = team, team.lib, int(world)
+        self.result = None
+        self.owned = handle is None
+        if handle is not None:
+            self.h = C.c_void_p(handle)
+            return
         h = C.c_void_p()
         code = self.lib.mplx_plpa_create(team.h, C.byref(h))
         if code != _capi.OK:
@@ -375,7 +386,7 @@ class PolyLpa:
 
     def __del__(self):
         try:
-            if self.h:
+            if self.h and self.owned:
                 self.lib.mplx_plpa_destroy(self.h)
                 self.h = None
         except Exception:
@@ -402,14 +413,19 @@ class PolyLpa:
         self.result = R
         return R.status == _capi.PLAN_OK
 
-    def update_nodes(self):
-        """PolyMapPlanner::updateNodes -> (entries that became blocked, entries that became free, [(entry, now blocked)] by entry number)"""
-        nb, nc, n = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        self.check(self.lib.mplx_plpa_update_nodes(self.h, self.world, C.byref(nb), C.byref(nc)))
+    def changed(self):
+        """[(entry, now blocked)] of the last updateNodes, by entry number"""
+        n = C.c_uint64()
         self.check(self.lib.mplx_plpa_changed(self.h, 0, None, None, C.byref(n)))
         e = np.zeros(max(n.value, 1), dtype=np.int32); b = np.zeros(max(n.value, 1), dtype=np.int32)
         self.check(self.lib.mplx_plpa_changed(self.h, n.value, e.ctypes.data, b.ctypes.data, C.byref(n)))
-        return int(nb.value), int(nc.value), list(zip(e[:n.value].tolist(), b[:n.value].tolist()))
+        return list(zip(e[:n.value].tolist(), b[:n.value].tolist()))
+
+    def update_nodes(self):
+        """PolyMapPlanner::updateNodes -> (entries that became blocked, entries that became free, [(entry, now blocked)] by entry number)"""
+        nb, nc = C.c_uint64(), C.c_uint64()
+        self.check(self.lib.mplx_plpa_update_nodes(self.h, self.world, C.byref(nb), C.byref(nc)))
+        return int(nb.value), int(nc.value), self.changed()
 
     def sub_state_space(self, time_step):
         self.check(self.lib.mplx_plpa_sub_state_space(self.h, self.world, int(time_step)))
@@ -452,3 +468,87 @@ class PolyLpa:
         self.check(self.lib.mplx_plpa_result_entries(self.h, max(m, 1), child.ctypes.data, parent.ctypes.data, action.ctypes.data, blocked.ctypes.data))
         return dict(n_nodes=n, states=states[:n], g=g[:n], rhs=rhs[:n], h=h[:n], closed=closed[:n], opened=opened[:n], built=built[:n],
                     child=child[:m], parent=parent[:m], action=action[:m], blocked=blocked[:m], initialized=self.initialized())
+
+
+class PolyLpaFleet:
+    """N PolyLpa planners on ONE PolyTeam (its lattice, limits, worlds and obstacles), member i bound to world world_of[i], whose
+    plan(), update_nodes() and sub_state_space() run for all members in one launch each (mplx_plpa_fleet_*): the fresh plans, the
+    repairs and the re-roots of different members side by side.  Per member every result is what the same sequence of calls on a
+    PolyLpa gives, bit for bit."""
+
+    def __init__(self, team, world_of):
+        self.team, self.lib = team, team.lib
+        self.world_of = [int(w) for w in world_of]
+        self.n = len(self.world_of)
+        w = np.ascontiguousarray(self.world_of, dtype=np.int32)
+        h = C.c_void_p()
+        code = self.lib.mplx_plpa_fleet_create(team.h, self.n, w.ctypes.data, C.byref(h))
+        if code != _capi.OK:
+            raise MplxError(f"mplx_plpa_fleet_create failed ({code})")
+        self.h = h
+        self.members = [PolyLpa(team, self.world_of[i], handle=self.lib.mplx_plpa_fleet_member(self.h, i)) for i in range(self.n)]
+        self.results = None
+
+    def __del__(self):
+        try:
+            if self.h:
+                for m in self.members:
+                    m.h = None
+                self.lib.mplx_plpa_fleet_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def check(self, code):
+        if code != _capi.OK:
+            raise MplxError(f"mplx error {code}: {self.lib.mplx_plpa_fleet_last_error(self.h).decode()}")
+
+    def member(self, i):
+        """member i as a PolyLpa (a view: the fleet owns the handle)"""
+        return self.members[i]
+
+    def set_capacity(self, nodes, edges, open_log):
+        self.check(self.lib.mplx_plpa_fleet_set_capacity(self.h, int(nodes), int(edges), int(open_log)))
+
+    def set_world(self, i, world):
+        self.check(self.lib.mplx_plpa_fleet_set_world(self.h, int(i), int(world)))
+        self.world_of[i] = self.members[i].world = int(world)
+
+    def plan(self, starts, goals, active=None, eps=1.0, tol_pos=0.5, tol_vel=-1.0, max_expand=-1, heur_ignore_dynamics=True):
+        """plan() of every (active) member, one launch; starts / goals: n x 9.  Returns the n results (zeroed for inactive members)."""
+        s = np.ascontiguousarray(starts, dtype=np.float64).reshape(self.n, 9)
+        g = np.ascontiguousarray(goals, dtype=np.float64).reshape(self.n, 9)
+        a = None if active is None else np.ascontiguousarray([1 if x else 0 for x in active], dtype=np.int32)
+        R = (_capi.Result * self.n)()
+        try:
+            self.check(self.lib.mplx_plpa_fleet_plan(self.h, s.ctypes.data, g.ctypes.data, None if a is None else a.ctypes.data, float(eps), float(tol_pos),
+                                                     float(tol_vel), int(max_expand), int(bool(heur_ignore_dynamics)), R))
+        finally:
+            self.results = [R[i] for i in range(self.n)]
+            for i, m in enumerate(self.members):
+                if a is None or a[i]:
+                    m.result = self.results[i]
+        return self.results
+
+    def update_nodes(self):
+        """updateNodes of every member that holds a space, one launch -> per member (n_blocked, n_cleared, [(entry, now blocked)])"""
+        nb = np.zeros(self.n, dtype=np.uint64); nc = np.zeros(self.n, dtype=np.uint64)
+        self.check(self.lib.mplx_plpa_fleet_update_nodes(self.h, nb.ctypes.data, nc.ctypes.data))
+        return [(int(nb[i]), int(nc[i]), self.members[i].changed()) for i in range(self.n)]
+
+    def sub_state_space(self, steps):
+        """getSubStateSpace(steps[i]) of member i (an int: of every member; < 0 leaves the member alone), one launch"""
+        st = np.ascontiguousarray([int(steps)] * self.n if np.isscalar(steps) else steps, dtype=np.int32)
+        self.check(self.lib.mplx_plpa_fleet_sub_state_space(self.h, st.ctypes.data))
+
+    def stats(self):
+        """of the last plan / sub_state_space: [members repaired, search launches, members planned afresh, members skipped]"""
+        st = np.zeros(4, dtype=np.uint32)
+        self.check(self.lib.mplx_plpa_fleet_stats(self.h, st.ctypes.data))
+        return [int(x) for x in st]
+
+    def last_kernel_ms(self):
+        """(kernel ms of the last search launch, of the last updateNodes launch)"""
+        a, b = C.c_float(), C.c_float()
+        self.check(self.lib.mplx_plpa_fleet_last_kernel_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
