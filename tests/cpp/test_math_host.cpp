@@ -37,14 +37,19 @@ static int fails = 0;
     }                               \
   } while (0)
 
+// a state, a control input and a duration: lattice-like values, and every 7th / 5th time the specials (signed zeros included)
+static double gen_case(int it, State &s, double *u) {
+  for (int i = 0; i < 12; i++) ((double *)&s)[i] = (it % 7 == 0) ? special((int)(rnd() % 12)) : round(uni(-3, 3) * 100) / 100;
+  for (int i = 0; i < 3; i++) u[i] = (it % 5 == 0) ? special((int)(rnd() % 12)) : (double)((int)(rnd() % 5) - 2) * 0.5;
+  return (it % 3 == 0) ? 1.0 : uni(0.1, 2.0);
+}
+
 template <int CONTROL>
 static void check_control(int iters) {
   for (int it = 0; it < iters; it++) {
     State s;
     double u[3];
-    for (int i = 0; i < 12; i++) ((double *)&s)[i] = (it % 7 == 0) ? special((int)(rnd() % 12)) : round(uni(-3, 3) * 100) / 100;
-    for (int i = 0; i < 3; i++) u[i] = (it % 5 == 0) ? special((int)(rnd() % 12)) : (double)((int)(rnd() % 5) - 2) * 0.5;
-    double T = (it % 3 == 0) ? 1.0 : uni(0.1, 2.0);
+    double T = gen_case(it, s, u);
     double c[3][6];
     for (int ax = 0; ax < 3; ax++) prim_build_axis(CONTROL, s.p[ax], s.v[ax], s.a[ax], s.j[ax], u[ax], c[ax]);
     // 1. specialised == generic at T, 0 and sample times
@@ -167,10 +172,14 @@ static void check_roots(int iters) {
   }
 }
 
+// the resolutions of the checks below: decimals, the float32-rounded values a VoxelMap message carries (every resolution of
+// tests/util.GEOMETRIES is among the two), and 2 / 255
+static const double RES[] = {0.1, 0.05, 0.2, 0.25, 0.3, 0.15, 0.01, 1.0 / 3, 0.07, 0.123456789, 1.0, 0.5,
+                             (double)0.1f, (double)0.05f, (double)0.2f, (double)0.15f, (double)0.3f, (double)0.01f, 2.0 / 255};
+
 // float_to_cell_inv (reciprocal + two FMAs, used in the voxel sampling loop) == float_to_cell (`/`)
 static void check_cell_quantisation(int iters) {
-  const double rs[] = {0.1, 0.05, 0.2, 0.25, 0.3, 0.15, 0.01, 1.0 / 3, 0.07, 0.123456789, 1.0, 0.5};
-  for (double r : rs) {
+  for (double r : RES) {
     const double inv = 1.0 / r;
     for (int it = 0; it < iters; it++) {
       double o = (it % 4 == 0) ? 0.0 : round(uni(-20, 20) * 10) / 10;
@@ -183,6 +192,59 @@ static void check_cell_quantisation(int iters) {
       }
       CHECK(same(div_by_inv(p - o, r, inv), (p - o) / r), "div_by_inv r %.17g d %.17g", r, p - o);
       CHECK(float_to_cell_inv(p, o, r, inv) == float_to_cell(p, o, r), "float_to_cell_inv r %.17g p %.17g o %.17g", r, p, o);
+    }
+  }
+}
+
+// ... with origins of both signs, off the cell lattice and tens of metres away (p - origin loses low bits), and points on cell
+// faces at negative cell indices
+static void check_cell_quantisation_offsets(int iters) {
+  static const double fixed[] = {-4.63, -2.57, -1.04, -3.13, 1.07, -0.52, 48.37, -37.21, 22.63, -5.113, -1.277, -0.0351, -0.075, 0.11};
+  for (double r : RES) {
+    const double inv = 1.0 / r;
+    for (int it = 0; it < iters; it++) {
+      double o;
+      switch (it % 3) {
+        case 0: o = fixed[(it / 3) % 14]; break;
+        case 1: o = uni(-80, 80); break;
+        default: o = (it & 8 ? -1.0 : 1.0) * round(uni(20, 80) * 100) / 100; break;
+      }
+      double p;
+      switch (it & 3) {
+        case 0: p = o + uni(-700, 700) * r; break;
+        case 1: p = round((o + uni(-700, 700) * r) * 100) / 100; break;   // lattice positions
+        case 2: p = o + (double)(int)uni(-6000, 100) * r; break;           // exactly on cell faces, mostly at negative indices
+        default: p = -(o + (double)(int)uni(0, 6000) * r); break;
+      }
+      CHECK(same(div_by_inv(p - o, r, inv), (p - o) / r), "div_by_inv (offsets) r %.17g d %.17g", r, p - o);
+      CHECK(float_to_cell_inv(p, o, r, inv) == float_to_cell(p, o, r), "float_to_cell_inv (offsets) r %.17g p %.17g o %.17g", r, p, o);
+    }
+  }
+}
+
+// the sampling loop's position (pos_at_qc_cell: pos_at_qc without its "+ 0.0" terms) through float_to_cell_inv gives the cell of
+// pos_at_qc through float_to_cell -- the claim of the comment above pos_at_qc_cell, with origin 0.0 (where a zero's sign could
+// matter) and with origins of both signs
+template <int CONTROL>
+static void check_cell_position(int iters) {
+  static const double origins[] = {0.0, -0.0, 0.05, -0.05, -4.63, 1.07, 48.37, -37.21, -0.0351};
+  for (int it = 0; it < iters; it++) {
+    State s;
+    double u[3];
+    const double T = gen_case(it, s, u);
+    const double r = RES[it % (int)(sizeof(RES) / sizeof(RES[0]))], inv = 1.0 / r;
+    for (int ax = 0; ax < 3; ax++) {
+      double c[6], qc[5];
+      prim_build_axis(CONTROL, s.p[ax], s.v[ax], s.a[ax], s.j[ax], u[ax], c);
+      pack_q_c<CONTROL>(c, qc);
+      const int n = 1 + (int)(rnd() % 40);
+      const double dt = T / n;
+      for (int i = 0; i <= n; i++) {
+        const double t = (double)i * dt;
+        for (double o : origins)
+          CHECK(float_to_cell_inv(pos_at_qc_cell<CONTROL>(qc, t), o, r, inv) == float_to_cell(pos_at_qc<CONTROL>(qc, t), o, r),
+                "pos_at_qc_cell ctrl %d r %.17g o %.17g t %.17g p %.17g", CONTROL, r, o, t, pos_at_qc<CONTROL>(qc, t));
+      }
     }
   }
 }
@@ -223,6 +285,11 @@ int main() {
   check_control<CTRL_SNP>(20000);
   check_heuristic(20000);
   check_roots<1>(2000); check_roots<2>(4000); check_roots<3>(6000); check_roots<4>(8000); check_roots<5>(8000); check_roots<6>(10000);
+  check_cell_quantisation_offsets(400000);
+  check_cell_position<CTRL_VEL>(20000);
+  check_cell_position<CTRL_ACC>(20000);
+  check_cell_position<CTRL_JRK>(20000);
+  check_cell_position<CTRL_SNP>(20000);
   printf("%s (%d failures)\n", fails ? "FAILED" : "OK", fails);
   return fails ? 1 : 0;
 }

@@ -25,28 +25,7 @@ def test_expand_batch_matches_get_succ(control):
     states = util.random_states(rng, 200, control, 0.3, 6.1)
     nodes = [util.gpu_wp(p, v, a, j, control, t=0.5 * i) for i, (p, v, a, j) in enumerate(states)]
     out = pl.getSuccBatch(nodes)
-    nU = U.shape[0]
-    total_reads = 0
-    P.reset_counters()
-    for k, (p, v, a, j) in enumerate(states):
-        cur = orc.waypoint(p, v, a, j, control, t=0.5 * k)
-        succ, cost, act = P.get_succ(cur)
-        got = [out[k * nU + i] for i in range(nU)]
-        got_valid = [g for g in got if g.valid]
-        assert [g.action for g in got_valid] == list(act)
-        for g, so, co in zip(got_valid, succ, cost):
-            assert g.cost == co or (np.isinf(g.cost) and np.isinf(co))
-            assert np.array_equal(np.array(g.wp.pos[:]), np.array(so.pos[:]))
-            assert np.array_equal(np.array(g.wp.vel[:]), np.array(so.vel[:]))
-            assert np.array_equal(np.array(g.wp.acc[:]), np.array(so.acc[:]))
-            assert np.array_equal(np.array(g.wp.jrk[:]), np.array(so.jrk[:]))
-            assert g.wp.t == so.t
-            key = (orc.C.c_int32 * 13)()
-            so.control = control
-            nk = orc.lib().orc_waypoint_key(orc.C.byref(so), key)
-            assert g.nkey == nk and list(g.key[:nk]) == list(key[:nk])
-        total_reads += sum(g.voxel_reads for g in got_valid)
-    assert total_reads == P.counters()["n_voxel_reads"]
+    util.compare_succ(P, out, states, control, U)  # (the comparison body is shared with tests/test_map_geometry.py)
 
 
 @pytest.mark.parametrize("control", [orc.ACC, orc.JRK])
@@ -199,17 +178,7 @@ def test_plan_batch_matches_single_queries(spec):
     starts = [util.gpu_wp(s) for s, g in queries]
     goals = [util.gpu_wp(g) for s, g in queries]
     res_b = pl.planBatch(starts, goals)
-    for q, (s, g) in enumerate(queries):
-        st = P.plan(orc.waypoint(s), orc.waypoint(g))
-        ids_o, _ = P.expanded()
-        r = res_b[q]
-        assert r.status == st
-        assert r.n_expanded == len(ids_o) and r.expand_hash == util.expand_hash(ids_o)
-        assert np.array_equal(pl.getExpandedIds(q), ids_o[: 1 << 15])
-        if st == 0:
-            assert r.cost == P.traj_cost
-            to, tg = P.traj(), pl.getTraj(q)
-            assert np.array_equal(tg.actions, to["actions"]) and np.array_equal(tg.node_ids, to["node_ids"])
+    util.compare_plan_batch(P, pl, queries, res_b, 1 << 15)
 
 
 @SPEC

@@ -14,17 +14,7 @@ def _oracle(grid, origin, res):
     return P
 
 
-def _disc_offsets(rn, hn):
-    ns = []
-    for nx in range(-rn, rn + 1):
-        for ny in range(-rn, rn + 1):
-            if np.hypot(nx, ny) > rn:
-                continue
-            for nz in range(-hn, hn + 1):
-                if nx == 0 and ny == 0 and nz == 0:
-                    continue
-                ns.append((nx, ny, nz))
-    return np.array(ns, dtype=np.int32)
+_disc_offsets = util.disc_offsets
 
 
 def test_oracle_dilate_does_not_cascade_and_clips_at_the_border():
@@ -69,23 +59,8 @@ def test_map_util_helpers_match_oracle(seed):
     mu = VoxelMapUtil()
     dz, dy, dx = grid.shape
     mu.setMap(origin, (dx, dy, dz), grid.ravel(), res)
-    # clouds before dilation: same points, same order
-    for which, fn in ((0, mu.getCloud), (1, mu.getFreeCloud), (2, mu.getUnknownCloud)):
-        a, b = fn(), P.cloud(which)
-        assert a.shape == b.shape and np.array_equal(a, b)
-    # dilate with the reference node's disc (map_planner_node.cpp:75-83) and a 3-D variant
-    for offs in (_disc_offsets(2, 0), _disc_offsets(1, 1)):
-        mu.dilate(offs)
-        P.dilate(offs)
-        assert np.array_equal(mu.getMap().reshape(grid.shape), P.get_map())
-    # cells
+    # clouds before dilation (same points, same order); dilate with the reference node's disc (map_planner_node.cpp:75-83) and a 3-D
+    # variant; cells; rays, some leaving the map; point queries on the dilated map (the bitmap was rebuilt)
     cells = rng.integers(-2, 66, size=(500, 3)).astype(np.int32)
-    st = mu.cellStates(cells)
-    assert st.tolist() == [P.cell_state(c) for c in cells]
-    # rays, some leaving the map
-    for _ in range(40):
-        a = rng.uniform(0.0, 6.4, 3); b = rng.uniform(-1.0, 7.4, 3)
-        assert np.array_equal(mu.rayTrace(a, b), P.ray_trace(a, b))
-    # a plan on the dilated map still agrees with the oracle (the bitmap was rebuilt)
-    cells0, st0 = mu.query(rng.uniform(0.2, 6.2, (200, 3)))
-    assert st0.tolist() == [P.cell_state(c) for c in cells0]
+    rays = [(rng.uniform(0.0, 6.4, 3), rng.uniform(-1.0, 7.4, 3)) for _ in range(40)]
+    util.compare_map_helpers(P, mu, grid, cells, rays, rng.uniform(0.2, 6.2, (200, 3)))

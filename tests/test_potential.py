@@ -114,10 +114,7 @@ def test_hip_distance_map_planner_flow_matches_the_oracle():
     gpath = [w.pos[:2] for w in pl.getTraj().getWaypoints()]
     assert np.array_equal(np.array(gpath), np.array(path)[:, :2])
 
-    def aux_of(mu):
-        out = np.empty(int(np.prod(mu._dim)), dtype=np.int8)
-        mu.ctx.check(mu.ctx.lib.mplx_aux_get(mu.ctx.h, out.ctypes.data))
-        return out
+    aux_of = util.aux_of
 
     # ---- the perturbed plan: search region around the path + potential (distance_map_planner_node.cpp:175-193)
     Q = oracle(0.5)
