@@ -115,7 +115,9 @@ typedef struct {
   uint64_t n_primitives, n_succ, n_succ_finite;
   uint64_t voxel_reads;
   uint64_t n_push, n_reopen;
-  uint64_t n_refill, n_evict; /* OPEN-structure maintenance events (diagnostics) */
+  uint64_t n_refill, n_evict; /* OPEN-structure maintenance events (diagnostics: how the search was run, not what it found.  n_refill
+                                 depends on the kernel and its version -- the speculative kernels drop stale entries at a pull and then
+                                 pull the next bucket sooner, mplx_result_open_dropped -- and is not part of the parity of a result) */
   uint64_t expand_hash; /* order-dependent hash of the expanded node ids (== same search) */
 } mplx_result;
 
@@ -557,6 +559,11 @@ int mplx_result_cycles(mplx_ctx *ctx, int q, uint64_t cyc[10]);
  * [3] units whose expansion was thrown away because their batch was cut ahead of them (they return to OPEN and are expanded again).
  * mplx_result.n_expanded counts committed units only: spec[2] - n_expanded is the work -- and traffic -- speculation wasted. */
 int mplx_result_speculation(mplx_ctx *ctx, int q, uint64_t spec[4]);
+/* Stale OPEN entries query q dropped where their far bucket was pulled into the near set (the speculative kernels; zero from every
+ * other kernel): entries of nodes improved or closed since they were pushed, which never became candidates.  Together with
+ * spec[1] -- the stale entries that did, because they went stale only after the pull -- these are all the stale entries the query
+ * met (the coarse-bucket activation drops none). */
+int mplx_result_open_dropped(mplx_ctx *ctx, int q, uint64_t *n_dropped);
 /* duration (ms, HIP events on the context's stream) of the last search / expand kernel launch */
 int mplx_last_kernel_ms(const mplx_ctx *ctx, float *ms);
 /* name of the search kernel mplx_plan / mplx_plan_batch launches for the current configuration */

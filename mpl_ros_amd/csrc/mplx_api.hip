@@ -1231,7 +1231,7 @@ static void fill_result(const QueryOut &o, mplx_result &r) {
   r.n_expanded = o.n_expanded; r.n_closed = o.n_closed; r.n_nodes = o.n_nodes; r.n_edges = o.n_edges;
   r.n_primitives = o.n_primitives; r.n_succ = o.n_succ; r.n_succ_finite = o.n_succ_finite;
   r.voxel_reads = o.voxel_reads; r.n_push = o.n_push; r.n_reopen = o.n_reopen;
-  r.n_refill = o.n_refill; r.n_evict = o.n_evict; r.expand_hash = o.expand_hash;
+  r.n_refill = query_refills(o); r.n_evict = o.n_evict; r.expand_hash = o.expand_hash;
 }
 
 // First half of a batch: marshal the queries, reset the per-batch device state, launch the search on the context's stream.
@@ -1950,6 +1950,12 @@ extern "C" int mplx_result_cycles(mplx_ctx *c, int q, uint64_t cyc[10]) {
 extern "C" int mplx_result_speculation(mplx_ctx *c, int q, uint64_t spec[4]) {
   if (!c || q < 0 || q >= c->last_nq || !spec) return fail(c, MPLX_ERR_ARG, "no such query");
   for (int i = 0; i < 4; i++) spec[i] = c->last_out[q].spec[i];
+  return MPLX_OK;
+}
+
+extern "C" int mplx_result_open_dropped(mplx_ctx *c, int q, uint64_t *n_dropped) {
+  if (!c || q < 0 || q >= c->last_nq || !n_dropped) return fail(c, MPLX_ERR_ARG, "no such query");
+  *n_dropped = query_open_dropped(c->last_out[q]);  // (QueryOut: zero from every kernel but the speculative ones)
   return MPLX_OK;
 }
 

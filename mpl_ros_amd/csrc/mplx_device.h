@@ -92,6 +92,8 @@ struct QueryOut {
   double cost;
   unsigned long long n_expanded, n_closed, n_nodes, n_edges, n_primitives, n_succ, n_succ_finite, voxel_reads, n_push,
       n_reopen, n_refill, n_evict, expand_hash;
+  // (n_refill: the refills in the low word; the speculative kernels put the stale OPEN entries they dropped at a pull into the high
+  // word -- mplx_result_open_dropped -- so that the record, and with it the code of every other kernel, stays what it was)
   unsigned long long t_begin, t_end;  // wall_clock64() ticks (100 MHz)
   unsigned long long cyc[10];         // s_memtime cycles: pop, expand, look-up, evict, refill, activate, commit; counts: batches, ordered batches, -
   uint32_t n_recorded, slot;
@@ -100,6 +102,9 @@ struct QueryOut {
   // them (they return to OPEN and are expanded again later).  n_expanded counts the committed units only.
   unsigned long long spec[4];
 };
+// the two halves of QueryOut::n_refill: every host reader goes through these
+__host__ __device__ inline unsigned long long query_refills(const QueryOut &o) { return o.n_refill & 0xFFFFFFFFull; }
+__host__ __device__ inline unsigned long long query_open_dropped(const QueryOut &o) { return o.n_refill >> 32; }
 
 // ---- helper workgroups (look-ahead expansion of a running query on otherwise idle compute units)
 // get_succ(node) and the heuristic of its successors are pure functions of (node state, U, dt, limits,

@@ -1172,8 +1172,52 @@ __device__ __forceinline__ void pull_fine_run(const QView<BLOCK, CONTROL, SM> &Q
   __syncthreads();
 }
 
-// near set empty: bring in the lowest far entries.  false when OPEN is empty.
+// Stale entries dropped where a far bucket is pulled (speculative kernels; refill<..., DROP>).  OPEN deletes lazily: a node that is
+// improved or closed leaves its old entry in the far buckets, and such an entry used to be pulled, ranked, taken as one of a batch's K
+// candidates and only then dropped (mplx_spec.h, step 2a) -- its unit idle for the whole batch.  Within a query g only decreases and
+// a closed node is re-opened only by a smaller g, so an entry that is stale once stays stale: dropping it here is the same pop that
+// skips it, earlier, and the pop order does not change.  The test is 2a's own (bits of the node's g against the entry's, FLAG_CLOSED;
+// plain loads -- every commit of the batches before lies behind a workgroup barrier).  One pass over near_[from, n_near) after the
+// walk: the loads of a round of BLOCK entries go out together (one memory trip; a run pull brings at most MERGE_TARGET entries), the
+// survivors are packed in place in their order.  The pass starts behind the sorted prefix near_[0, n_sorted) a top-up pulls behind
+// (with the pulled entries it sees the few pushed since the last selection: a top-up finds fewer than K entries in all), and
+// nothing is carried across the walk for it.  A pull that evicted (evict_half has replaced the threshold refill had just reset)
+// re-packed the whole near set: all of it is filtered, and the caller clears n_sorted as before.
 template <int BLOCK, int CONTROL, class SM>
+__device__ __forceinline__ void drop_stale(const QView<BLOCK, CONTROL, SM> &Q, int tid) {
+  using V = QView<BLOCK, CONTROL, SM>;
+  SM &S = Q.S;
+  const uint32_t n = S.n_near, from = S.ts_id != 0xFFFFFFFFu ? 0u : S.n_sorted;
+  if (from >= n) return;  // (uniform) nothing behind the prefix
+  uint32_t w = from;      // (uniform) where the next survivor goes: w <= base in every round, so a round only overwrites what it has read
+  for (uint32_t base = from; base < n; base += BLOCK) {
+    const uint32_t i = base + (uint32_t)tid;
+    double ef = 0.0, eg = 0.0;
+    uint32_t eid = 0, eix = 0;
+    bool keep = false;
+    if (i < n) {
+      ef = S.near_f[i]; eg = S.near_g[i]; eid = S.near_id[i]; eix = S.near_idx[i];
+      char *rec = Q.node(eid);
+      keep = __double_as_longlong(V::g(rec)) == __double_as_longlong(eg) && !(V::flags(rec) & FLAG_CLOSED);
+    }
+    uint32_t kept;
+    const uint32_t pos = w + block_excl_scan<BLOCK>(keep ? 1u : 0u, S, tid, kept);  // (its barriers lie between the reads above and the writes below)
+    if (keep) {
+      S.near_f[pos] = ef; S.near_g[pos] = eg; S.near_id[pos] = eid; S.near_idx[pos] = eix;
+    }
+    w += kept;
+  }
+  __syncthreads();  // (everybody has read n_near)
+  if (tid == 0) {
+    S.c_drop += n - w;
+    S.n_near = w;
+  }
+  __syncthreads();
+}
+
+// near set empty: bring in the lowest far entries.  false when OPEN is empty.  DROP (speculative kernels): the entries a pull of
+// fine buckets appends go through drop_stale; a pull that leaves nothing is followed by the next bucket like an empty one.
+template <int BLOCK, int CONTROL, class SM, bool DROP = false>
 __device__ __forceinline__ bool refill(const QView<BLOCK, CONTROL, SM> &Q, int tid) {
   SM &S = Q.S;
   // buckets one pull may take together: MERGE_CUR sub-list cursors per thread (none for the narrow one-node kernels)
@@ -1208,6 +1252,7 @@ __device__ __forceinline__ bool refill(const QView<BLOCK, CONTROL, SM> &Q, int t
         __syncthreads();
         if (S.pull_n > 1) pull_fine_run(Q, tid);
         else pull_bucket(Q, b0, tid);
+        if constexpr (DROP) drop_stale(Q, tid);
       } else {
         if (tid == 0) {
           S.cur0 = b0;
@@ -1218,6 +1263,7 @@ __device__ __forceinline__ bool refill(const QView<BLOCK, CONTROL, SM> &Q, int t
         }
         __syncthreads();
         pull_bucket(Q, b0, tid);
+        if constexpr (DROP) drop_stale(Q, tid);
       }
       MPLX_TOC(S, 4, t0);
       if (S.n_near > 0) return true;

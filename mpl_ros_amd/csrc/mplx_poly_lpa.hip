@@ -244,7 +244,7 @@ int plpa_plan_finish(mplx_plpa *l, const PlpaQuery &q, const double *goal, mplx_
     out->status = o.status; out->traj_len = o.traj_len; out->cost = o.cost;
     out->n_expanded = o.n_expanded; out->n_closed = o.n_closed; out->n_nodes = o.n_nodes; out->n_edges = o.n_edges;
     out->n_primitives = o.n_primitives; out->n_succ = o.n_succ; out->n_succ_finite = o.n_succ_finite;
-    out->n_push = o.n_push; out->n_refill = o.n_refill; out->n_evict = o.n_evict; out->expand_hash = o.expand_hash;
+    out->n_push = o.n_push; out->n_refill = query_refills(o); out->n_evict = o.n_evict; out->expand_hash = o.expand_hash;
   }
   if (o.status == MPLX_PLAN_POOL_FULL || o.status == MPLX_PLAN_INTERNAL) {
     l->valid = false;

@@ -101,6 +101,7 @@ struct SmemSpec : Smem<UL * K, K, NCAP_> {
   int32_t u_goal[K];  // candidate k satisfies the goal test (evaluated ahead of its commit)
   int32_t u_cut[K];   // first later candidate preceded by an entry unit k pushes (K if none)
   uint32_t n_sorted;  // near_[0, n_sorted) is in ascending order (left so by the previous selection)
+  uint32_t c_drop;    // stale entries dropped where their far bucket was pulled (mplx_kernels.h drop_stale): they never became candidates
   // the entries appended since, sorted (selection scratch)
   unsigned long long hpow[17];  // powers of the expansion-hash multiplier (0x100000001B3^e mod 2^64), filled once per workgroup
   double app_f[256], app_g[256];
@@ -609,6 +610,10 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
   const V Q{P, S, P.bkt_head + (size_t)blockIdx.x * 2 * NB * NSUB};
   constexpr int nk = key_len_c(CONTROL), ns = key_len_c(CONTROL);
   constexpr int NKY = nk + (YAW ? 1 : 0), EX = YAW ? 1 : 0;  // key integers / extra state doubles (the yaw) of a record
+  // stale OPEN entries dropped where their far bucket is pulled (mplx_kernels.h drop_stale): every build but the 125-input jerk
+  // kernel with helpers, which pays for the pass with 85 more spilled VGPRs and ran its batch 3 % slower with it
+  // (profiles/open_stale_filter_speed.txt): that build keeps the parent's refill
+  constexpr bool DROP = !(HELP && CONTROL == CTRL_JRK && UL == 128);
   // key of a lane's successor incl. the yaw key, its 64-bit hash
   auto lane_hash = [&](const LaneSucc &l) {
     if constexpr (YAW) {
@@ -675,7 +680,7 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
       S.arr_max = 0; S.arr_heur = 0; S.sum_heur = 0; S.sum_arr = 0;
       S.dbg_n = S.dbg_na = S.dbg_slow = S.dbg_n256 = S.dbg_pulls = 0;
 #endif
-      S.c_cand = S.c_live = S.c_cut = 0;
+      S.c_cand = S.c_live = S.c_cut = S.c_drop = 0;
       S.cur_id = NIL;
       S.helped = 0;
       S.box_seq = 0;
@@ -793,7 +798,7 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
         batch_no++;
         if (S.n_near == 0) {
           __syncthreads();
-          if (!refill(Q, tid)) {
+          if (!refill<BLOCK, CONTROL, SM, DROP>(Q, tid)) {
             if (tid == 0) S.status = 1;  // OPEN empty
             __syncthreads();
             break;
@@ -806,7 +811,7 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
         for (int guard = 0; guard < 8 && S.n_near < (uint32_t)K; guard++) {
           __syncthreads();
           const uint32_t before = S.n_near;
-          if (!refill(Q, tid)) break;
+          if (!refill<BLOCK, CONTROL, SM, DROP>(Q, tid)) break;
           if (tid == 0 && S.c_evict != evict0) S.n_sorted = 0;  // only an eviction inside the pull reorders; appends keep the prefix
           (void)before;
           __syncthreads();
@@ -1741,6 +1746,7 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
       query_report<EX>(Q, q, goal_id, [&](uint32_t, uint32_t action) {
         return (POT && P.map.aux) ? P.ucost[action & EDGE_ACTION_MASK] + P.pot_weight * (double)(action >> EDGE_POT_SHIFT) : P.ucost[action & EDGE_ACTION_MASK];
       }, SpecCounts{{S.c_cand, S.c_cand - S.c_live, S.c_live, S.c_cut}}, t_begin, ld_state);
+      P.out[q].n_refill |= (unsigned long long)S.c_drop << 32;  // (QueryOut: the high word; query_refills / query_open_dropped)
 #ifdef MPLX_LOOKUP_TIMERS
       if (P.nq == 1 || q % 61 == 0) {  // (a batch: a sample of its queries -- a thousand workgroups printing at once tear each other's lines)
       printf("cyc2 q%d batches %llu:", q, S.cyc[7]);

@@ -819,6 +819,14 @@ class VoxelMapPlanner:
         ctx.check(ctx.lib.mplx_result_speculation(ctx.h, q, sp))
         return dict(zip(("candidates", "stale", "units_expanded", "units_cut"), [int(x) for x in sp[:4]]))
 
+    def queryOpenDropped(self, q=0):
+        """Stale OPEN entries query q dropped where their far bucket was pulled (mplx_result_open_dropped): they never became
+        candidates, so querySpeculation's "stale" counts only the entries that went stale after the pull."""
+        ctx = self._ctx()
+        n = C.c_uint64(0)
+        ctx.check(ctx.lib.mplx_result_open_dropped(ctx.h, q, C.byref(n)))
+        return int(n.value)
+
     # ---- results
     def getTrajCost(self):
         return self.traj_cost_
