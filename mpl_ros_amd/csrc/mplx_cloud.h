@@ -43,6 +43,10 @@
 //   E8  get_succ skips a primitive when tn == curr (same state key), when validate_primitive fails or when isFree fails
 //       (E1, then E2-E6): no infinite-cost successors, n_succ == n_succ_finite.  Cost J(control) + w dt.  The start is
 //       always free (env_cloud::is_free returns true).  Expanded nodes are not recorded (env_cloud.h:57 is commented out).
+//   E9  points that are not finite: a point with a NaN or infinite coordinate, or one whose float coordinate overflows
+//       (1e300) or whose squared float distance does (1e30), fails dist < r2f in E2, so it blocks nothing and changes
+//       no other decision; its cell coordinate is clamped (NaN to -2^40).  This project's choice: what PCL does with
+//       such a cloud is not known here.
 #pragma once
 #include "mplx_kernels.h"
 

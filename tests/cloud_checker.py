@@ -4,7 +4,9 @@ and of the A* loop around it, in the evaluation order of the E-list (mpl_ros_amd
 
 Primitive build / evaluate / max_vel / validate / J, the state key, the heuristic and the goal test come from the CPU
 restatement of the voxel path (oracle/orc.py).  The point test is done here with a plain host grid (every point within
-two radii of a sample centre is looked at), not with the product's index.  Test infrastructure only.
+two radii of a sample centre is looked at), not with the product's index.  Cloud(..., brute=True) builds no grid at all: every
+point of the cloud goes through the radius filter, so a comparison with it has no index on either side that could be wrong in
+the same way, and points that are not finite are accepted.  Test infrastructure only.
 """
 import ctypes as C
 import heapq
@@ -83,9 +85,11 @@ def inside(ci, d, pts):
 class Cloud:
     """EllipsoidUtil(r) with setObstacles(obs) (every point kept: the box has no planes yet) and setBoundingBox(ori, dim)"""
 
-    def __init__(self, obs, r, ori, dim):
+    def __init__(self, obs, r, ori, dim, brute=False):
         self.pd = np.ascontiguousarray(np.asarray(obs, dtype=np.float64).reshape(-1, 3))
-        self.pf = self.pd.astype(np.float32)
+        with np.errstate(all="ignore"):  # (1e300 becomes float32 inf)
+            self.pf = self.pd.astype(np.float32)
+        self.brute = bool(brute)
         self.r = float(r)
         self.rf = np.float32(self.r)
         self.r2f = np.float32(float(self.rf) * float(self.rf))
@@ -95,7 +99,8 @@ class Cloud:
         # host grid of edge 2 r over the float coordinates: a point the filter accepts is within r (1 + 2^-20) of the centre
         self.cell = 2.0 * float(self.rf)
         self.grid = {}
-        if len(self.pd):
+        self.all = np.arange(len(self.pd), dtype=np.int64)
+        if len(self.pd) and not self.brute:
             keys = np.floor(self.pf.astype(np.float64) / self.cell).astype(np.int64)
             order = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
             ks = keys[order]
@@ -104,6 +109,8 @@ class Cloud:
                 self.grid[tuple(ks[a])] = order[a:b]
 
     def candidates(self, cf):
+        if self.brute:  # grid-free: the radius filter sees every point
+            return self.all
         c = [math.floor(float(x) / self.cell) for x in cf]
         idx = [self.grid.get((c[0] + i, c[1] + j, c[2] + k)) for i in (-1, 0, 1) for j in (-1, 0, 1) for k in (-1, 0, 1)]
         idx = [a for a in idx if a is not None]
@@ -119,9 +126,10 @@ class Cloud:
             return False
         self.tests += len(idx)
         pf = self.pf[idx]
-        dx, dy, dz = pf[:, 0] - cf[0], pf[:, 1] - cf[1], pf[:, 2] - cf[2]
-        dist = (dx * dx + dy * dy) + dz * dz
-        cand = idx[dist < self.r2f]
+        with np.errstate(all="ignore"):  # (brute mode: inf - inf, inf * inf and NaN fail the comparison, as on the device)
+            dx, dy, dz = pf[:, 0] - cf[0], pf[:, 1] - cf[1], pf[:, 2] - cf[2]
+            dist = (dx * dx + dy * dy) + dz * dz
+            cand = idx[dist < self.r2f]
         if len(cand) == 0:
             return False
         Cm, _ = ellipsoid_C(self.axe, acc)

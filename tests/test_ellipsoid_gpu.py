@@ -12,6 +12,7 @@ from mpl_ros_amd.ellipsoid import EllipsoidPlanner, control_lattice, state13
 from oracle import orc
 from tests import cloud_checker as K
 from tests import cloud_scenes as S
+from tests.cloud_compare import _compare_plan, _compare_succ
 
 pytestmark = pytest.mark.gpu
 
@@ -67,17 +68,6 @@ def _near_surface_cloud(rng, ck, states, r, n_pts=400):
             u /= np.linalg.norm(u)
             pts.append(d + Cm @ (u * sgn))
     return np.array(pts)
-
-
-def _compare_succ(pl, ck, states):
-    valid, succ, cost, act = pl.get_succ_batch(states)
-    for k, s13 in enumerate(states):
-        for i, (ok, st, c, a) in enumerate(ck.get_succ(s13)):
-            assert bool(valid[k, i]) == ok, (k, i)
-            assert act[k, i] == a
-            assert np.array_equal(succ[k, i], st), (k, i, succ[k, i], st)
-            assert (math.isinf(c) and math.isinf(cost[k, i])) or cost[k, i] == c, (k, i)
-    return int(valid.sum())
 
 
 @pytest.mark.parametrize("control", [orc.ACC, orc.JRK])
@@ -162,29 +152,6 @@ def _office_planner(control=orc.ACC, use_3d=False):
     pl.set_epsilon(L["eps"])
     pl.set_tol(*L["tol"])
     return pl, ck
-
-
-def _compare_plan(pl, ck, start, goal, max_num=-1):
-    pl.set_max_num(max_num)
-    pl.set_record(1 << 16)
-    ok = pl.plan(start, goal)
-    r = pl.result()
-    c = ck.plan(start, goal, eps=L["eps"], tol_pos=L["tol"][0], tol_vel=L["tol"][1], tol_acc=L["tol"][2], max_num=max_num)
-    assert r["status"] == c["status"]
-    assert r["n_expanded"] == len(c["expanded"])
-    assert list(pl.expanded_ids()) == c["expanded"]
-    assert r["expand_hash"] == K.expand_hash(c["expanded"])
-    assert r["n_nodes"] == len(c["states"])
-    st, g, closed, opened = pl.nodes()
-    assert sorted(map(tuple, st[closed, :3])) == sorted(tuple(s[:3]) for s, cl in zip(c["states"], c["closed"]) if cl)
-    assert np.array_equal(st, np.array(c["states"]))
-    if ok:
-        assert r["cost"] == c["cost"]
-        tr = pl.get_traj()
-        assert np.array_equal(tr["states"], c["traj"]["states"])
-        assert tr["actions"].tolist() == c["traj"]["actions"]
-    assert len(pl.get_expanded_nodes()) == 0
-    return r, c
 
 
 def test_office_plan_matches_the_checker():
