@@ -372,7 +372,7 @@ extern "C" int mplx_poly_plan_batch(mplx_poly *p, int32_t n, const int32_t *worl
   P.poly_world = p->d_world_of;
   // look-ahead helpers: only when every leader has exactly one query (the batched tick) and the masks fit one word
   int n_help = 0;
-  if (p->helpers != 0 && n <= slots && p->n_u <= 31 && c->n_cus > slots) {
+  if (p->helpers != 0 && n <= slots && p->n_u <= 31 && c->n_cus > slots) {  // P8 (mplx_poly_dev.h)
     n_help = (c->n_cus - slots) / slots;
     const int want = p->helpers < 0 ? 4 : p->helpers;  // (measured on the Team2 tick: 3 per robot already serve 99.9 % of the pops)
     if (n_help > want) n_help = want;

@@ -249,7 +249,7 @@ MPLX_HD MPLX_NOINLINE int solve_any6(double a, double b, double c, double d, dou
 }
 template <bool GEN>
 MPLX_HD int solve_poly(double a, double b, double c, double d, double e, double f, double *ts) {
-  if constexpr (GEN) {
+  if constexpr (GEN) {  // P9
     if (a != 0 || b != 0 || c != 0) return solve_any6(a, b, c, d, e, f, ts);
   }
   return solve_le2(a, b, c, d, e, f, ts);
@@ -451,6 +451,18 @@ MPLX_HD int obs_prim_hits(const PolyDev &D, const double cs[2][6], double T, con
 // arithmetic expression and every sum order is the one of the functions above (the boolean results are OR-ed, which
 // has no order); an "unsupported degree" only counts when the reference's loop would have reached it before a hit.
 // [one lane per pair, all loops serial, took 50 k cycles per expansion: 78 % of a search]
+//
+// The switches between the decomposed test and the code it falls back to, numbered for the tests that cross each one on
+// purpose (tests/poly_scenes.py, tests/test_poly_geometry.py):
+//   P1  n_obs > POLY_MAX_OBS: one lane per pair with the serial collide(); poly_stage_world does not stage
+//   P2  a primitive's span overlaps more than POLY_SLOTS trajectory segments: mode 4, the serial collide() for that obstacle
+//   P3  sum of hyperplanes > POLY_LDS_HPS or sum of segments > POLY_LDS_SEGS: the world stays in global memory, cum == nullptr
+//   P4  HP <= 15, n_pairs <= 1023, *ilen <= ICAP: the dense item list, else the rectangular index space
+//   P5  PolyObs::fast (with cum): short evaluation forms, the id0 scan start, reach from disp
+//   P6  PolyObs::radius == +inf (poly_radius, mplx_poly.inl): no pruning for that obstacle; the rx / ry test otherwise
+//   P7  the per-level cache: a level k in [0, POLY_CACHE_LEVELS), the tags (query + 1, bits of t_rel), lds_level
+//   P8  n_u <= 31 (host, mplx_poly_plan_batch): helper workgroups, whose masks hold the hit bits 0..30
+//   P9  GEN: solve_any6 rather than solve_le2
 constexpr int POLY_SLOTS = 3;     // trajectory segments one primitive may overlap here (more: that pair runs the serial collide())
 constexpr int POLY_MAX_OBS = 64;  // obstacles prepared per node (a world with more runs the serial collide() per pair)
 struct PolySlot {
@@ -479,6 +491,8 @@ constexpr int POLY_CACHE_LEVELS = 64;
 // id0: a segment known to start at or before `time` (0 when nothing is known).  With strictly increasing segment start
 // times the scan from id0 finds the segment the scan from 0 finds; callers pass id0 > 0 only for such trajectories
 // (PolyObs::fast) and only together with cum.
+// (With durations >= 0 the same holds for any trajectory: every segment before id0 ends at or before the time asked for, so the scan
+// from 0 skips them too; the restriction to fast trajectories is a precaution, not a need.)
 MPLX_HD void traj_pos(const PolySeg *segs, int n_seg, double total_t, double time, double pos[2], const double *cum = nullptr, int id0 = 0) {
   pos[0] = pos[1] = 0.0;
   if (n_seg <= 0) return;
@@ -536,7 +550,7 @@ MPLX_HD void poly_prepare_time(const PolyDev &D, const PolyObs &o, double prT, d
   }
   const PolySeg *segs = D.segs + o.seg_off;
   const double *cum = D.cum ? D.cum + o.cum_off : nullptr;
-  const bool fast = o.fast && cum;
+  const bool fast = o.fast && cum;  // P5
   const double traj_t = t + o.start_t;
   int start_id = -1;
   double T = 0.0;
@@ -567,7 +581,7 @@ MPLX_HD void poly_prepare_time(const PolyDev &D, const PolyObs &o, double prT, d
     const double t_residual = T - traj_t < 0 ? 0 : T - traj_t;
     const double start_t = t_residual <= 0 ? traj_t : T;
     if (t_residual > prT) break;
-    if (R.n_slots == POLY_SLOTS) { R.mode = 4; break; }
+    if (R.n_slots == POLY_SLOTS) { R.mode = 4; break; }  // P2
     PolySlot &S = R.slot[R.n_slots++];
     S.T = T; S.t_residual = t_residual; S.start_t = start_t; S.seg_T = segs[id].T;
     if (fast) {  // (start_t lies inside segment id: what traj_eval's scan finds; VEL / ACC segment, lt >= 0: the short forms)
@@ -708,7 +722,7 @@ __device__ __forceinline__ void poly_collide_all(const PolyDev &D, const PolyWor
   const int n_obs = W.n_obs;
   unsigned long long tc0 = __builtin_readcyclecounter();
   const double x0 = pp_p_auto(cs[0][0], 0.0), y0 = pp_p_auto(cs[0][1], 0.0);  // pr.evaluate(0): the node position, whatever the primitive
-  if (n_obs > POLY_MAX_OBS) {  // (uniform) a crowded world: one lane per pair, the reference's loops as they are
+  if (n_obs > POLY_MAX_OBS) {  // P1 (uniform) a crowded world: one lane per pair, the reference's loops as they are
     for (int j = tid; j < n_obs; j += BLOCK)
       if (obs_point_hits(D, D.obs[W.obs_off + j], x0, y0, t_rel)) *start_hit = 1;
     const int pairs = n_u * n_obs;
@@ -735,7 +749,7 @@ __device__ __forceinline__ void poly_collide_all(const PolyDev &D, const PolyWor
   // 368-byte entry word by word cost most of this phase); a level that is already in LDS is not copied at all
   const unsigned long long tbits = (unsigned long long)__double_as_longlong(t_rel);
   PolyPrep *level = nullptr;
-  if (D.prep_cache && T > 0 && cache_q != 0) {  // (uniform)
+  if (D.prep_cache && T > 0 && cache_q != 0) {  // P7 (uniform)
     const double lv = t_rel / T;
     const int k = lv >= 0 && lv < (double)POLY_CACHE_LEVELS ? (int)(lv + 0.5) : -1;
     if (k >= 0 && k < POLY_CACHE_LEVELS) level = D.prep_cache + ((size_t)(D.prep_slice0 + (int)blockIdx.x) * POLY_CACHE_LEVELS + (size_t)k) * POLY_MAX_OBS;
@@ -775,6 +789,7 @@ __device__ __forceinline__ void poly_collide_all(const PolyDev &D, const PolyWor
     if (!valid[i] || prep[j].mode == 0) continue;
     bool keep = true;
     const PolyPrep &R = prep[j];
+    // P6
     if (R.reach < INFINITY && lead_pzero(cs[i][0]) && lead_pzero(cs[i][1])) {
       const double rx = fabs(cs[i][0][4]) * T + 0.5 * fabs(cs[i][0][3]) * T * T + R.reach + POLY_PRUNE_EPS;
       const double ry = fabs(cs[i][1][4]) * T + 0.5 * fabs(cs[i][1][3]) * T * T + R.reach + POLY_PRUNE_EPS;
@@ -792,6 +807,7 @@ __device__ __forceinline__ void poly_collide_all(const PolyDev &D, const PolyWor
   const int n_list = can_list ? (int)*plen : n_pairs;
   uint32_t *ilist = uns_idx + POLY_MAX_U * POLY_MAX_OBS / 2, *ilen = &uns_idx[POLY_MAX_U * POLY_MAX_OBS - 2];
   constexpr int ICAP = POLY_MAX_U * POLY_MAX_OBS / 2 - 2;
+  // P4
   const bool dense = can_list && n_pairs <= POLY_MAX_U * POLY_MAX_OBS / 2 && POLY_SLOTS <= 15 && HP <= 15;
   if (dense) {
     if (tid == 0) *ilen = 0u;
@@ -884,7 +900,7 @@ __device__ __forceinline__ void poly_stage_world(const PolyDev &D, const PolyWor
   WL = W;
   if (tid == 0) {
     int nh = 0, ns = 0;
-    bool fits = W.n_obs <= POLY_MAX_OBS;
+    bool fits = W.n_obs <= POLY_MAX_OBS;  // P1, P3
     for (int j = 0; j < W.n_obs && fits; j++) {
       const PolyObs &o = D.obs[W.obs_off + j];
       nh += o.n_hp;

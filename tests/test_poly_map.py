@@ -9,6 +9,7 @@ import pytest
 
 from mpl_ros_amd import poly_map as pm
 from oracle import refpoly
+from tests.poly_compare import compare_get_succ as _compare_get_succ, compare_plans as _compare_plans  # (shared with test_poly_geometry.py)
 
 needs_ref = pytest.mark.skipif(not refpoly.available(), reason="oracle/_ref/libpolymap_ref.so not built (make -C oracle ref)")
 
@@ -57,21 +58,6 @@ def test_reference_environment_known_answers():
     assert len(R.get_succ([9.0, 4.0, 2.0, 0.0, 0, 0, 0, 0, 0.0])[2]) < 9  # v_max: u_x = 1 would exceed 2 m/s
 
 
-def _compare_get_succ(team, worlds, refs, world_of, states, n_u):
-    out = team.get_succ_batch(world_of, states)
-    n_inf = n_fin = 0
-    for k, (w, s) in enumerate(zip(world_of, states)):
-        succ, cost, act = refs[w].get_succ(s)
-        got = [out[k * n_u + i] for i in range(n_u)]
-        gv = [g for g in got if g.valid]
-        assert [g.action for g in gv] == act.tolist(), (k, w)
-        for g, so, co in zip(gv, succ, cost):
-            assert np.array_equal(np.array(g.state[:]), so), (k, g.action)        # bit-exact f64
-            assert g.cost == co or (np.isinf(g.cost) and np.isinf(co)), (k, g.action, g.cost, co)
-            n_inf += int(np.isinf(co)); n_fin += int(np.isfinite(co))
-    return n_fin, n_inf
-
-
 @pytest.mark.gpu
 @needs_ref
 @pytest.mark.parametrize("seed", range(4))
@@ -114,31 +100,6 @@ def test_team2_tick_get_succ_matches_the_compiled_reference():
         states[r * 40] = starts_t[r]
     n_fin, n_inf = _compare_get_succ(team, worlds, refs, world_of, states, 9)
     assert n_fin > 1000 and n_inf > 100
-
-
-def _compare_plans(team, refs, world_of, starts, goals, compare_acc=False, **kw):
-    cols = [0, 1, 2, 3, 4, 5, 8] if compare_acc else [0, 1, 2, 3, 8]  # (JRK states carry their acceleration)
-    team.set_record(1 << 16)
-    R = team.plan_batch(world_of, starts, goals, **kw)
-    n_ok = 0
-    for k, w in enumerate(world_of):
-        ref = refs[w].plan(starts[k], goals[k], eps=kw.get("eps", 1.0), tol_pos=kw.get("tol_pos", 0.5), max_expand=kw.get("max_expand", -1),
-                           heur_ignore_dynamics=kw.get("heur_ignore_dynamics", True))
-        r = R[k]
-        assert r.status == ref["status"], (k, r.status, ref["status"])
-        assert r.n_expanded == len(ref["expanded"]) and r.n_nodes == ref["n_nodes"], (k, r.n_expanded, len(ref["expanded"]), r.n_nodes, ref["n_nodes"])
-        assert np.array_equal(team.expanded_ids(k), ref["expanded"]), k  # same nodes in the same order
-        if ref["status"] == 0:
-            n_ok += 1
-            assert r.cost == ref["cost"], (k, r.cost, ref["cost"])  # bit-exact f64
-            act, ids, st = team.traj(k)
-            assert np.array_equal(act, ref["actions"]) and np.array_equal(ids, ref["node_ids"]), k
-            for i, nid in enumerate(ids):  # waypoint states: position, velocity and time of every node of the path
-                s, _, _ = refs[w].node(int(nid))
-                assert np.array_equal(st[i][cols], s[cols]), (k, i)
-        else:
-            assert np.isinf(r.cost)
-    return R, n_ok
 
 
 @pytest.mark.gpu
