@@ -17,6 +17,9 @@
  * J + 0.001 J(VEL) + w dt, :71-73).  2-D like every in-tree caller (multi_robot_node.cpp, poly_map_planner_node.cpp); a
  * PolyMapPlanner3D (poly_map_planner.h:107, robot.hpp:229) plans through mplx_poly3_* instead, by way of the reference-free
  * plumbing of poly3_device.h, and serves getCloseSet / getOpenSet / getExpandedNodes from the device (3-D LPA* is refused).
+ * A 2-D planner serves getCloseSet / getOpenSet / getExpandedNodes / getValidPrimitives / getAllPrimitives from the device as
+ * well (poly_map_planner_node.cpp:105-124, poly_map_replanner_node.cpp:156-158,184,234), through the reference-free
+ * poly2_space.h: lazily from the shared device object in A* mode, from its own LPA* handle with setLPAstar(true).
  * With setLPAstar(true) (poly_map_replanner_node.cpp:352) the planner keeps a device-resident LPA* state space of its own
  * (mplx_plpa_*): updateNodes() (:61-93) re-tests every stored predecessor primitive against the obstacles as they are now and
  * fills getBlockedPrimitives / getClearedPrimitives, plan() repairs, getSubStateSpace(k) re-roots (round 6).
@@ -28,6 +31,7 @@
 #include <mpl_planner/common/planner_base.h>
 #include <mplx.h>
 
+#include "poly2_space.h"
 #include "poly3_device.h"
 
 #include <vector>
@@ -90,6 +94,7 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
     cleared_prs_.clear();
     if (Dim == 3) { refuse3("updateNodes()"); return; }
     if (!lpa_ || !mplx_plpa_initialized(lpa_)) return;  // (if (!this->ss_ptr_) return;)
+    space_ = mplx_shim::Poly2Space();
     mplx_poly *p = shared_poly_device();
     if (!p || !upload(p, lpa_control_)) return;
     uint64_t nb = 0, nc = 0, n = 0;
@@ -116,6 +121,7 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
   void getSubStateSpace(int time_step) {
     if (Dim == 3) { refuse3("getSubStateSpace()"); return; }
     if (!lpa_ || !mplx_plpa_initialized(lpa_)) return;
+    space_ = mplx_shim::Poly2Space();
     mplx_poly *p = shared_poly_device();
     if (!p || !upload(p, lpa_control_)) return;
     lcheck(mplx_plpa_sub_state_space(lpa_, 0, time_step));
@@ -129,6 +135,9 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
     this->traj_ = Trajectory<Dim>();
     this->traj_cost_ = std::numeric_limits<decimal_t>::infinity();
     res_ = mplx_result();
+    space_ = mplx_shim::Poly2Space();
+    plan_epoch_ = 0;
+    space_control_ = (int32_t)start.control & 15;
     if (Dim == 3 && has_map_) return plan3(start, goal);
     if (Dim != 2 || !has_map_) {
       printf(ANSI_COLOR_RED "[PolyMapPlanner] plan() refused: the mplx back-end plans 2-D moving-obstacle searches after setMap()\n" ANSI_COLOR_RESET);
@@ -147,6 +156,7 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
     const int32_t world = 0;
     uint64_t *cap = shared_poly_capacity();
     if (this->use_lpastar_) return plan_lpastar(start, s9, g9, control);
+    if (!check(p, mplx_poly_set_record(p, 1u << 20))) return false;  // (expansion order of the first 2^20 expansions: getExpandedNodes)
     for (int attempt = 0;; attempt++) {
       if (!check(p, mplx_poly_set_capacity(p, 1, cap[0], cap[1], cap[2]))) return false;
       if (!check(p, mplx_poly_plan_batch(p, 1, &world, s9, g9, this->epsilon_, this->tol_pos_, this->tol_vel_, this->max_num_,
@@ -155,6 +165,7 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
       for (int k = 0; k < 3; k++) cap[k] *= 2;  // (the reference grows std containers: grow the device pools and search again)
       printf(ANSI_COLOR_CYAN "[PolyMapPlanner] device pools exhausted: doubled, planning again\n" ANSI_COLOR_RESET);
     }
+    plan_epoch_ = mplx_poly_plan_epoch(p);  // (the getters answer while this is still the device object's last plan)
     if (res_.status == MPLX_PLAN_START_OCCUPIED) { printf(ANSI_COLOR_RED "[PlannerBase] start is not free!\n" ANSI_COLOR_RESET); return false; }
     this->traj_cost_ = res_.cost;
     if (res_.status != MPLX_PLAN_OK || std::isinf(res_.cost)) {
@@ -184,19 +195,63 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
     if (Dim == 3 && use_lpastar) refuse3("setLPAstar(true)");
     Base::setLPAstar(use_lpastar);
   }
-  /// the state space / expansion order of the last 3-D plan, from the device (2-D: PlannerBase's)
-  vec_Vecf<Dim> getCloseSet() const override { return Dim == 3 ? set3(1) : Base::getCloseSet(); }
-  vec_Vecf<Dim> getOpenSet() const override { return Dim == 3 ? set3(0) : Base::getOpenSet(); }
+  /// the state space / expansion order of the last plan, from the device.  2-D: positions in id order (upstream walks its hash
+  /// map hm_: the order of its sets is unspecified), the expanded states in expansion order; a failed plan's sets too
+  /// (poly_map_planner_node.cpp:105)
+  vec_Vecf<Dim> getCloseSet() const override { return Dim == 3 ? set3(1) : set2(1, "getCloseSet()"); }
+  vec_Vecf<Dim> getOpenSet() const override { return Dim == 3 ? set3(0) : set2(0, "getOpenSet()"); }
   vec_Vecf<Dim> getExpandedNodes() const override {
-    if (Dim != 3) return Base::getExpandedNodes();
+    if (Dim != 3) return set2(2, "getExpandedNodes()");
     vec_Vecf<Dim> ps;
     for (int32_t id : plan3_.expanded) ps.push_back(pos3((size_t)id));
     return ps;
   }
+  /// Primitive(parent state, U[action], dt) of every predecessor record with finite cost / of every record, the blocked ones
+  /// included (poly_map_replanner_node.cpp:184,234).  3-D: refused, not served.
+  vec_E<Primitive<Dim>> getValidPrimitives() const override { return primitives2(false, "getValidPrimitives()"); }
+  vec_E<Primitive<Dim>> getAllPrimitives() const override { return primitives2(true, "getAllPrimitives()"); }
 
  protected:
   void refuse3(const char *what) const {
     printf(ANSI_COLOR_RED "[PolyMapPlanner] %s refused: the mplx back-end has no 3-D LPA* (PolyMapPlanner3D plans with A* only)\n" ANSI_COLOR_RESET, what);
+  }
+  /// the 2-D state space of the last plan on the host (poly2_space.h), fetched at the first getter that asks; false: nothing to serve
+  bool space2(bool with_blocked, const char *what) const {
+    if (Dim != 2) return false;
+    if (this->use_lpastar_) return lpa_ && mplx_shim::poly2_space_fetch_lpa(lpa_, res_, space_);
+    if (plan_epoch_ == 0) return false;  // (no plan of this planner ran on the device: empty sets, as upstream before plan())
+    return mplx_shim::poly2_space_fetch(shared_poly_device(), 0, plan_epoch_, res_, with_blocked, space_, what);
+  }
+  vec_Vecf<Dim> set2(int which, const char *what) const {
+    vec_Vecf<Dim> ps;
+    if (!space2(false, what)) return ps;
+    const std::vector<double> xy = space_.positions(which);
+    for (size_t i = 0; i + 1 < xy.size(); i += 2) {
+      Vecf<Dim> p = Vecf<Dim>::Zero();
+      p(0) = xy[i]; p(1) = xy[i + 1];
+      ps.push_back(p);
+    }
+    return ps;
+  }
+  vec_E<Primitive<Dim>> primitives2(bool all, const char *what) const {
+    vec_E<Primitive<Dim>> prs;
+    if (Dim == 3) {
+      printf(ANSI_COLOR_RED "[PolyMapPlanner] %s refused: the mplx back-end serves the predecessor primitives of 2-D plans only (PolyMapPlanner3D: getCloseSet / getOpenSet / getExpandedNodes)\n" ANSI_COLOR_RESET, what);
+      return prs;
+    }
+    if (!space2(all, what)) return prs;
+    auto add = [&](int32_t parent, int32_t action) {
+      if (parent < 0 || (size_t)parent >= space_.n_nodes() || action < 0 || (size_t)action >= this->U_vec_.size()) return;
+      const double *st = &space_.states[(size_t)parent * 9];
+      Waypoint<Dim> w((Control::Control)space_control_);
+      for (int k = 0; k < 2; k++) { w.pos(k) = st[k]; w.vel(k) = st[2 + k]; w.acc(k) = st[4 + k]; w.jrk(k) = st[6 + k]; }
+      w.t = st[8];
+      prs.push_back(Primitive<Dim>(w, this->U_vec_[(size_t)action], this->dt_));
+    };
+    for (size_t i = 0; i < space_.parent.size(); i++) add(space_.parent[i], space_.action[i]);
+    if (all)
+      for (size_t i = 0; i < space_.blocked_parent.size(); i++) add(space_.blocked_parent[i], space_.blocked_action[i]);
+    return prs;
   }
   Vecf<Dim> pos3(size_t id) const {
     Vecf<Dim> p;
@@ -384,6 +439,9 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
   mplx_result res_ = mplx_result();
   mplx_plpa *lpa_ = nullptr;  // the LPA* state space of this planner (setLPAstar(true)), created by its first plan()
   int32_t lpa_control_ = MPLX_ACC;
+  mutable mplx_shim::Poly2Space space_;  // the 2-D state space of the last plan, fetched by the first getter that asks
+  uint64_t plan_epoch_ = 0;             // mplx_poly_plan_epoch of the shared device object right after this planner's A* plan (0: none)
+  int32_t space_control_ = MPLX_ACC;
   mplx_shim::Poly3Plan plan3_;  // what the last 3-D plan left on the host (trajectory, state space, expansion order)
 };
 

@@ -27,8 +27,9 @@ class PlannerBase {
   Trajectory<Dim> getTraj() const { return traj_; }
   decimal_t getTrajCost() const { return traj_cost_; }
   /// primitives of the pred entries of the state-space mirror: finite cost only / all (poly_map_replanner_node.cpp:184,234)
-  vec_E<Primitive<Dim>> getValidPrimitives() const { return mirror_primitives(false); }
-  vec_E<Primitive<Dim>> getAllPrimitives() const { return mirror_primitives(true); }
+  /// (virtual: a planner that serves them from the device -- PolyMapPlanner -- is reached through a base pointer too)
+  virtual vec_E<Primitive<Dim>> getValidPrimitives() const { return mirror_primitives(false); }
+  virtual vec_E<Primitive<Dim>> getAllPrimitives() const { return mirror_primitives(true); }
   /// positions handed to get_succ, in order (env_base::expanded_nodes_)
   virtual vec_Vecf<Dim> getExpandedNodes() const { return ENV_ ? ENV_->get_expanded_nodes() : vec_Vecf<Dim>(); }
   virtual vec_Vecf<Dim> getCloseSet() const { return mirror_set(true); }

@@ -463,6 +463,28 @@ int mplx_poly_result_traj(mplx_poly *p, int32_t q, int32_t *actions, int32_t *no
 int mplx_poly_set_record(mplx_poly *p, uint32_t cap_per_query);
 int mplx_poly_result_expanded(mplx_poly *p, int32_t q, uint32_t cap, int32_t *ids, uint32_t *n);
 int mplx_poly_last_kernel_ms(const mplx_poly *p, float *ms);
+/* The state space of query q of the last mplx_poly_plan_batch (getCloseSet / getOpenSet / getValidPrimitives / getAllPrimitives of
+ * PlannerBase, planner_base.h:30-35,86-104), exported by kernels straight from the device pools: only the arrays asked for cross the
+ * bus (any output pointer may be NULL), and one export per (plan, q) is kept on the device, so the three calls for one query share the
+ * first pass.  Served after MPLX_PLAN_OK / _NO_PATH / _MAX_EXPAND / _TRAJ_TOO_LONG -- a failed plan's closed set too
+ * (poly_map_planner_node.cpp:105); a query that created no state (occupied start, start at the goal) gives MPLX_OK, nothing written,
+ * *n = 0.  Refused (MPLX_ERR_ARG, text in mplx_poly_last_error): MPLX_PLAN_POOL_FULL / _INTERNAL queries (their last records may be
+ * half built), q outside the last batch, a pending launch, released pools.
+ * _nodes: the n_nodes states in id order -- states n x 9 (pos2 vel2 acc2 jrk2 t: the first-arrival state and its time as the record
+ *   stores them), g, h, closed / opened flags; cap < n_nodes: MPLX_ERR_CAPACITY, nothing written.
+ * _edges: the predecessor records, children in id order, each child's records oldest first (the order of mplx_result_edges: the
+ *   reference's push_back order); *n is always the full count, at most cap entries are written (cap = 0: a pure count query).
+ * _blocked: the successors with cost +inf of the states closed at the end of the search, one (parent, action) per blocked primitive,
+ *   parents in id order, actions ascending; cap / *n as _edges.  The batched A* does not materialise them (deviation D7, as the voxel
+ *   search): they are re-derived on request -- get_succ is a pure function of state, lattice, limits and world -- and the call is
+ *   refused when that would run against anything but the planned world (mplx_poly_config or mplx_poly_commit ran since the plan). */
+int mplx_poly_result_nodes(mplx_poly *p, int32_t q, uint64_t cap, double *states, double *g, double *h, int32_t *closed, int32_t *opened);
+int mplx_poly_result_edges(mplx_poly *p, int32_t q, uint64_t cap, int32_t *child, int32_t *parent, int32_t *action, uint64_t *n);
+int mplx_poly_result_blocked(mplx_poly *p, int32_t q, uint64_t cap, int32_t *parent, int32_t *action, uint64_t *n);
+/* (measurement) kernel time of the last first pass (nodes + their scan), edges pass and blocked pass the three calls above ran */
+int mplx_poly_result_space_ms(mplx_poly *p, float ms[3]);
+/* plan launches of the handle so far: a wrapper sharing the handle notices that another planner has planned on it since */
+uint64_t mplx_poly_plan_epoch(const mplx_poly *p);
 /* Look-ahead helper workgroups of mplx_poly_plan_batch (no reference counterpart: the reference runs one planner per
  * thread of control): when every leader workgroup has one query -- the batched tick -- workgroups on the otherwise idle
  * compute units run the collision tests of the states a search has just created, before the search pops them (the

@@ -7,6 +7,7 @@ bool mplx_launch_poly_get_succ(bool general, int grid, hipStream_t s, const mplx
 bool mplx_launch_poly_search(int control, bool general, int block, int grid, hipStream_t s, const mplx::SearchParams &P);
 
 #include "mplx_poly_lpa_host.h"
+#include "mplx_poly_space.h"
 struct mplx_poly {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -44,6 +45,10 @@ struct mplx_poly {
   int world_cap = 0;
   mplx::PolyPrep *d_prep_cache = nullptr;  // per workgroup x time level x obstacle (mplx_poly_dev.h)
   int prep_cache_slots = 0;
+  // state-space export of the last batch (mplx_poly_result_nodes / _edges / _blocked: mplx_poly_space.hip)
+  uint64_t cfg_epoch = 0;                             // counts mplx_poly_config calls
+  uint64_t plan_cfg_epoch = 0, plan_commit_epoch = 0;  // what the last plan ran under
+  mplx_poly_space *space = nullptr;
 };
 
 static int pfail(mplx_poly *p, int code, const char *fmt, ...) {
@@ -91,6 +96,7 @@ extern "C" void mplx_poly_destroy(mplx_poly *p) {
   (void)hipFree(p->d_U);
   (void)hipFree(p->d_world_of);
   (void)hipFree(p->d_prep_cache);
+  mplx_poly_space_free(p->space);
   (void)hipFree(p->d_help_mask); (void)hipFree(p->d_help_ring); (void)hipFree(p->d_help_pub);
   if (p->help_stream) (void)hipStreamDestroy(p->help_stream);
   if (p->help_ev) (void)hipEventDestroy(p->help_ev);
@@ -114,6 +120,7 @@ extern "C" int mplx_poly_config(mplx_poly *p, int32_t control, int32_t n_u, cons
   PCHK(p, hipMemcpyAsync(p->d_U, p->U.data(), sizeof(double) * 2 * (size_t)n_u, hipMemcpyHostToDevice, p->stream));
   PCHK(p, hipStreamSynchronize(p->stream));
   p->have_cfg = true;
+  p->cfg_epoch++;
   return MPLX_OK;
 }
 
@@ -266,6 +273,34 @@ extern "C" int mplx_poly_internal_view(mplx_poly *p, mplx_poly_view *out) {
   out->commit_epoch = p->commit_epoch;
   return MPLX_OK;
 }
+
+// (internal: mplx_poly_space.h) the view the state-space export works with
+int mplx_poly_space_internal_view(mplx_poly *p, mplx_poly_space_view *out) {
+  if (!p || !out) return MPLX_ERR_ARG;
+  const mplx_ctx *c = p->ctx;
+  out->dev = poly_dev(p);
+  out->general = poly_general(p) ? 1 : 0;
+  out->device = p->device;
+  out->stream = c->stream;
+  out->last_nq = c->last_nq;
+  out->pending = c->pending ? 1 : 0;
+  out->pools_valid = c->pools_valid ? 1 : 0;
+  out->recycled = c->last_recycled ? 1 : 0;
+  out->pool_control = c->pool_control;
+  out->last_out = c->last_out.data();
+  out->node_pool = c->pools.node_pool; out->edge_pool = c->pools.edge_pool;
+  out->node_chunks = c->pools.node_chunks; out->edge_chunks = c->pools.edge_chunks;
+  out->node_tables = c->d_node_tables; out->edge_tables = c->d_edge_tables;
+  out->world_of = p->d_world_of;
+  out->plan_epoch = c->plan_epoch;
+  out->commit_epoch = p->commit_epoch; out->plan_commit_epoch = p->plan_commit_epoch;
+  out->cfg_epoch = p->cfg_epoch; out->plan_cfg_epoch = p->plan_cfg_epoch;
+  out->space = &p->space;
+  return MPLX_OK;
+}
+int mplx_poly_space_internal_fail(mplx_poly *p, int code, const char *msg) { return pfail(p, code, "%s", msg); }
+// plan launches of the handle so far (a wrapper that shares the handle notices that somebody else planned on it since)
+extern "C" uint64_t mplx_poly_plan_epoch(const mplx_poly *p) { return p ? p->ctx->plan_epoch : 0; }
 
 extern "C" int mplx_poly_get_succ_batch(mplx_poly *p, int32_t K, const int32_t *world_of, const double *states, mplx_poly_succ *out) {
   if (!p || K <= 0 || !world_of || !states || !out) return pfail(p, MPLX_ERR_ARG, "bad argument");
@@ -475,6 +510,8 @@ extern "C" int mplx_poly_plan_batch(mplx_poly *p, int32_t n, const int32_t *worl
   c->last_dt = p->dt;
   c->last_U = c->U;
   c->plan_epoch++;
+  p->plan_cfg_epoch = p->cfg_epoch;
+  p->plan_commit_epoch = p->commit_epoch;
   for (int k = 0; k < n; k++)
     if (out[k].status == MPLX_PLAN_INTERNAL) return pfail(p, MPLX_ERR_ARG, "internal: a hyperplane equation of degree > 2 was met by the quadratic-only kernel");
   return MPLX_OK;

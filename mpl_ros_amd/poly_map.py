@@ -238,6 +238,62 @@ class PolyTeam:
         self.check(self.lib.mplx_poly_result_expanded(self.h, q, cap, ids.ctypes.data, C.byref(n)))
         return ids[:n.value]
 
+    def plan_epoch(self):
+        """plan launches of the handle so far"""
+        return int(self.lib.mplx_poly_plan_epoch(self.h))
+
+    def state_space(self, q):
+        """The state space of query q of the last plan_batch, exported on the device (mplx_poly_result_nodes / _edges): states n x 9
+        (pos2 vel2 acc2 jrk2 t) in id order, g, h, closed / opened flags, and the predecessor records (child, parent, action), children
+        in id order, each child's records oldest first.  The names are those of PolyLpa.state_space()."""
+        q = int(q)
+        n = int(self._results[q].n_nodes)
+        states = np.zeros((max(n, 1), 9)); g = np.zeros(max(n, 1)); h = np.zeros(max(n, 1))
+        closed = np.zeros(max(n, 1), dtype=np.int32); opened = closed.copy()
+        self.check(self.lib.mplx_poly_result_nodes(self.h, q, n, states.ctypes.data, g.ctypes.data, h.ctypes.data, closed.ctypes.data, opened.ctypes.data))
+        ne = C.c_uint64()
+        self.check(self.lib.mplx_poly_result_edges(self.h, q, 0, None, None, None, C.byref(ne)))
+        m = int(ne.value)
+        child = np.zeros(max(m, 1), dtype=np.int32); parent = child.copy(); action = child.copy()
+        if m:
+            self.check(self.lib.mplx_poly_result_edges(self.h, q, m, child.ctypes.data, parent.ctypes.data, action.ctypes.data, C.byref(ne)))
+        return dict(n_nodes=n, states=states[:n], g=g[:n], h=h[:n], closed=closed[:n], opened=opened[:n],
+                    child=child[:m], parent=parent[:m], action=action[:m])
+
+    def blocked(self, q):
+        """(parent, action) of the successors with cost +inf of the states closed at the end of query q's search, parents in id order,
+        actions ascending (mplx_poly_result_blocked: re-derived on the device; refused once the worlds or the set-up have changed)."""
+        q = int(q)
+        nb = C.c_uint64()
+        self.check(self.lib.mplx_poly_result_blocked(self.h, q, 0, None, None, C.byref(nb)))
+        m = int(nb.value)
+        parent = np.zeros(max(m, 1), dtype=np.int32); action = parent.copy()
+        if m:
+            self.check(self.lib.mplx_poly_result_blocked(self.h, q, m, parent.ctypes.data, action.ctypes.data, C.byref(nb)))
+        return parent[:m], action[:m]
+
+    def space_kernel_ms(self):
+        """(measurement) kernel ms of the last first pass (nodes + scan), edges pass and blocked pass of the state-space export"""
+        ms = (C.c_float * 3)()
+        self.check(self.lib.mplx_poly_result_space_ms(self.h, ms))
+        return [float(x) for x in ms]
+
+    def _flag_positions(self, q, want_closed):
+        q = int(q)
+        n = int(self._results[q].n_nodes)
+        states = np.zeros((max(n, 1), 9)); closed = np.zeros(max(n, 1), dtype=np.int32); opened = closed.copy()
+        self.check(self.lib.mplx_poly_result_nodes(self.h, q, n, states.ctypes.data, None, None, closed.ctypes.data, opened.ctypes.data))
+        sel = closed[:n] != 0 if want_closed else (opened[:n] != 0) & (closed[:n] == 0)
+        return states[:n][sel][:, 0:2].copy()
+
+    def close_set(self, q):
+        """getCloseSet(): positions of the states with the closed flag, in id order"""
+        return self._flag_positions(q, True)
+
+    def open_set(self, q):
+        """getOpenSet(): positions of the states that are opened and not closed, in id order"""
+        return self._flag_positions(q, False)
+
     def cycles(self, q):
         """shader-clock cycles query q spent in pop / get_succ / look-up + commit"""
         cyc = (C.c_uint64 * 10)()
