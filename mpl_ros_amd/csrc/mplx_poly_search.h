@@ -198,7 +198,8 @@ __global__ __launch_bounds__(BLOCK) void astar_poly_kernel(SearchParams P) {
         __syncthreads();
         MPLX_TOC(S, 3, tx);
         // isFree(start.pos, t) and isFree(pr, t) of all primitives against all obstacles
-        auto hook = [&]() {  // the table slot has arrived: start fetching the record it names (the commit reads it)
+        auto hook = [&]() {  // the table slot has arrived: meant to start fetching the record it names (the commit reads it) -- but
+                             // __builtin_prefetch emits no instruction on gfx950, so the fetch starts at the commit (mplx_spec.h, 2c)
                                   const uint32_t vid = (uint32_t)v0;
                                   if (vid < CLAIM_BASE && (v0 >> 32) == (tbl_tagq(h64, (uint32_t)q, P.tbl_epoch) >> 32))
                                     __builtin_prefetch(Q.node(vid), 0, 3);

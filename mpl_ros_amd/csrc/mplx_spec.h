@@ -57,6 +57,9 @@
 //     LIVE ones, so that stale entries -- 13 % of the candidates -- do not cost a unit its slot: identical results, tail 2273 vs 2027 ms,
 //     bulk 139.6 vs 135.2 ms (profiles/r06h_ab_refill_negative.json): one more barrier, 27 spilled VGPRs, and a fresh push inside the
 //     first 2 K entries shifts every later one away from the record its half unit had prefetched -- an exposed refetch in most batches.
+#ifndef MPLX_X_KEY_HASH
+#define MPLX_X_KEY_HASH 1     // (HELP builds, units inside one wave) key_hash64 of a candidate's key computed once per batch (KeyHashLds::cur_hash), not at every use
+#endif
 #ifndef MPLX_X_PROBE2
 #define MPLX_X_PROBE2 1       // (round 6) the look-up's first load brings the home slot AND its neighbour (almost always the same 64-byte line): a
                               // key whose home slot is taken by another state no longer costs the slowest lane of the batch a second dependent trip
@@ -73,8 +76,19 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// key_hash64 of candidate k's key (MPLX_X_KEY_HASH): written in 2a by the lane that checks the look-ahead record, read by the row
+// check, the pair tags and the successor test.  Only the builds that use it hold the words (N = K there, 0 elsewhere: an empty member
+// that takes no LDS).
+template <int N>
+struct KeyHashLds {
+  unsigned long long cur_hash[N];
+};
+template <>
+struct KeyHashLds<0> {};
+
 // YAW: yaw-carrying states -- one more key integer (round(yaw / 0.1)) behind the control kind's own
-template <int UL, int K, int CONTROL, int BTN, int NCAP_, bool YAW = false>
+// NHASH: per-unit key hashes kept in LDS (KeyHashLds above)
+template <int UL, int K, int CONTROL, int BTN, int NCAP_, bool YAW = false, int NHASH = 0>
 struct SmemSpec : Smem<UL * K, K, NCAP_> {
   static constexpr int BLOCK = UL * K, BT = BTN, NK = key_len_c(CONTROL) + (YAW ? 1 : 0);
   static_assert(NK <= MAX_KEY, "yaw-carrying SNP states (13 key integers) stay on the one-node kernel");
@@ -124,6 +138,7 @@ struct SmemSpec : Smem<UL * K, K, NCAP_> {
   uint32_t n_work;
   uint32_t work[WISH];          // pool indices of the node records to expand ahead of time
   unsigned long long wish_l[WISH];
+  [[no_unique_address]] KeyHashLds<NHASH> kh;  // (behind the product build's other words, which keep their offsets)
 #ifdef MPLX_LOOKUP_TIMERS
   unsigned long long cyc2[24];
   unsigned long long cycw[16][4];
@@ -599,7 +614,10 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
   static_assert(!(HELP && POT), "the look-ahead cache rows carry no potential sums");
   static_assert(!(YAW && (HELP || POT)), "yaw-carrying searches run without helpers and without an auxiliary map");
   constexpr int BLOCK = UL * K;
-  using SM = SmemSpec<UL, K, CONTROL, BTN, NCAP_, YAW>;
+  // one key hash per candidate and batch, kept in LDS (without yaw the record's key and the state's are the same nk integers; a
+  // unit that spans waves, <128,4,JRK,help>, keeps its code)
+  constexpr bool KEY_LDS = MPLX_X_KEY_HASH && HELP && !YAW && UL <= 64;
+  using SM = SmemSpec<UL, K, CONTROL, BTN, NCAP_, YAW, KEY_LDS ? K : 0>;
   constexpr int BT = SM::BT;
   __shared__ SM S;
   using V = QView<BLOCK, CONTROL, SM>;
@@ -1156,8 +1174,17 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
         if constexpr (HELP) {
           // did a helper expand this node ahead of time?  The entry must be of THIS state: the helper's hash of the
           // key of the state it expanded against the candidate's own key (guards against anything stale on its side)
+          // (KEY_LDS: the same lane leaves the hash in S.kh.cur_hash for the rest of the batch -- the row check, the successor test --
+          //  behind the unit_sync below; a chain of 64-bit multiplies over the key's LDS words that used to be redone at each use)
+          unsigned long long hk_rec = 0ull;
+          if constexpr (KEY_LDS) {
+            if (live_unit && lu == UL - 1) {
+              hk_rec = key_hash64(S.cur_key[ku], nk);
+              S.kh.cur_hash[opaque(ku)] = hk_rec;
+            }
+          }
           if (live_unit && S.helped && !MPLX_XF(P, 256) && lu == UL - 1 && (uint32_t)hc_a != 0u && ((uint32_t)hc_b & CACHE_READY) &&  // [MPLX_X_FLAGS & 256, diagnostics: no hit is taken]
-              (uint32_t)(hc_a >> 32) == (uint32_t)key_hash64(S.cur_key[ku], nk)) {
+              (uint32_t)(hc_a >> 32) == (KEY_LDS ? (uint32_t)hk_rec : (uint32_t)key_hash64(S.cur_key[ku], nk))) {
             S.hc_row[ku] = (uint32_t)hc_a;
             S.hc_valid[ku] = (uint32_t)hc_b;
             S.hc_blocked[ku] = (uint32_t)(hc_b >> 32);
@@ -1291,7 +1318,9 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
           if (rp1 && !MPLX_ROW_FENCE(P) && !MPLX_XF(P, 1024)) {  // [MPLX_X_FLAGS & 1024, measurement: the row is not checked (round 3's protocol)]
             const double *row = P.cache_h + (size_t)(rp1 - 1u) * cache_row_doubles(UL);
             const bool want = act && P.eps != 0.0;  // (the lanes whose heuristic was asked for: the record's masks are L.valid / L.blocked now)
-            const uint32_t khash = (uint32_t)key_hash64(S.cur_key[ku], nk);
+            uint32_t khash;
+            if constexpr (KEY_LDS) khash = (uint32_t)S.kh.cur_hash[ku];
+            else khash = (uint32_t)key_hash64(S.cur_key[ku], nk);
             for (uint32_t polls = 0;; polls++) {
               const uint32_t cs = unit32_xor(want ? cache_row_term(h_row, lu) : 0u);
               const uint32_t rd = (uint32_t)__shfl((int)(uint32_t)reads_word, 0, 32), stored = (uint32_t)__shfl((int)(uint32_t)(reads_word >> 32), 0, 32);
@@ -1340,9 +1369,14 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
             const uint32_t claim_batch = (batch_no & CLAIM_BATCH_MASK) << CLAIM_BATCH_SHIFT;
             static_assert(BLOCK <= (1 << CLAIM_BATCH_SHIFT), "the thread index of a claim has nine bits");
             const unsigned long long claim = tagq | (unsigned long long)(CLAIM_BASE + claim_batch + (uint32_t)tid);
-            // second round trip (claim the empty slot, or fetch the record the slot names) goes out
-            // before the heuristic is computed, so its latency hides behind the f64 work.  (Computing the
-            // heuristic only for states found to be new, after the look-up, was measured slower: the slowest
+            // The claim of an empty slot goes out before the heuristic is computed, so that compare-and-swap's trip hides
+            // behind the f64 work.  The record a taken slot names does NOT: __builtin_prefetch emits no instruction on gfx950
+            // (a slot load, a prefetch of the record and the record load compile to two global_loads and nothing else), so the
+            // fetch of an existing state's record starts inside the probe loop, after the heuristic.  A real early load of one
+            // word of the record (consumed behind the record's own loads) was measured and not kept: bulk 127.0 against
+            // 125.6 ms, one more live register in a kernel that spills (profiles/key_hash_lds_speed.txt).  The call stays
+            // where it is: it costs nothing, and without it the compiler schedules every build of this kernel differently.
+            // (Computing the heuristic only for states found to be new, after the look-up, was measured slower: the slowest
             // lane of the workgroup sets the pace either way, and the overlap is lost.)
             unsigned long long cas0 = 0;
             bool did_cas0 = false;
@@ -1350,7 +1384,7 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
               cas0 = atomicCAS(&P.table[pos], v0, claim);
               did_cas0 = true;
             } else if ((uint32_t)v0 < CLAIM_BASE && (v0 & 0xFFFFFFFF00000000ull) == tagq) {
-              __builtin_prefetch(Q.node((uint32_t)v0), 0, 3);
+              __builtin_prefetch(Q.node((uint32_t)v0), 0, 3);  // (no instruction on gfx950: see above)
             }
             MPLX_T2(S, 2, t2);
             if (P.eps != 0.0) {
@@ -1361,7 +1395,9 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
               {
 #if MPLX_X_ROW_PAIRS
                 if constexpr (UL == 32) {  // this lane's {heuristic, check}: what does not match yet is a store on its way
-                  const uint32_t kh = (uint32_t)key_hash64(S.cur_key[ku], nk);
+                  uint32_t kh;
+                  if constexpr (KEY_LDS) kh = (uint32_t)S.kh.cur_hash[ku];
+                  else kh = (uint32_t)key_hash64(S.cur_key[ku], nk);
                   const double *row = P.cache_h + (size_t)(S.hc_row[ku] - 1u) * cache_row_doubles(UL);
                   for (uint32_t polls = 0; cache_pair_tag((unsigned long long)__double_as_longlong(h_row), kh, (uint32_t)q, P.epoch, (uint32_t)lu) != h_tag; polls++) {
                     if (polls >= CACHE_ROW_POLLS) { S.status = 5; break; }
@@ -1466,7 +1502,9 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
 #if MPLX_X_EARLY_ROW && MPLX_X_ROW_PAIRS
         if constexpr (HELP && UL == 32) {  // the helper's voxel-read count of a cached unit, once its pair checks out
           if (lu == 0 && live_unit && S.hc_row[ku] != 0u) {
-            const uint32_t kh = (uint32_t)key_hash64(S.cur_key[ku], nk);
+            uint32_t kh;
+            if constexpr (KEY_LDS) kh = (uint32_t)S.kh.cur_hash[ku];
+            else kh = (uint32_t)key_hash64(S.cur_key[ku], nk);
             const double *row = P.cache_h + (size_t)(S.hc_row[ku] - 1u) * cache_row_doubles(UL);
             for (uint32_t polls = 0; cache_pair_tag(reads_word, kh, (uint32_t)q, P.epoch, 63u) != reads_tag; polls++) {
               if (polls >= CACHE_ROW_POLLS) { S.status = 5; break; }
@@ -1485,7 +1523,9 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
         // does a candidate itself appear among the successors of the batch?  (its closed flag must
         // reach the units committed after it)
         if (lu == 0 && live_unit) {
-          const unsigned long long hk = key_hash64(S.cur_key[ku], NKY);
+          unsigned long long hk;
+          if constexpr (KEY_LDS) hk = S.kh.cur_hash[ku];
+          else hk = key_hash64(S.cur_key[ku], NKY);
           const unsigned long long hv = hk | 1ull;
           int sl = (int)(hk >> 7) & (BT - 1);
           for (;;) {
