@@ -1353,7 +1353,9 @@ static int plan_batch_launch(mplx_ctx *c, int nq, const mplx_waypoint *starts, c
     c->help_cache_filled = true;
     // launch epoch: every word the helpers poll is tagged with it, so nothing left over from the previous launch
     // can be mistaken for progress of this one
-    c->help_epoch++;
+    // (a kept cache keeps its epoch: the check word of a row is salted with it, and a kept row must pass the leader's row check --
+    //  the boxes and the done word, the other carriers of the epoch, are rewritten above and below)
+    if (!kept) c->help_epoch++;
     if (c->help_epoch == 0) c->help_epoch = 1;
     P.epoch = c->help_epoch;
     c->help_done_init = (unsigned long long)P.epoch << 32;

@@ -30,10 +30,13 @@
 #define MPLX_X_LDS_CONST 1    // control inputs, edge costs in LDS; goal test against the LDS copy of the goal
 #endif
 #ifndef MPLX_X_EARLY_SETUP
-#define MPLX_X_EARLY_SETUP 1  // next batch's set-up (resets, chunk capacity, helper announcement) inside the end-of-batch bookkeeping
+#define MPLX_X_EARLY_SETUP 1  // next batch's set-up (resets, chunk capacity, the helpers' expansion count) inside the end-of-batch bookkeeping
 #endif
 #ifndef MPLX_X_EARLY_ROW
 #define MPLX_X_EARLY_ROW 1    // look-ahead cache row (heuristics, voxel-read count) requested as soon as the row is known
+#endif
+#ifndef MPLX_X_WISH_NOW
+#define MPLX_X_WISH_NOW 1     // a wish list is announced by the lane that finishes writing it, not by the set-up of the next batch (a batch of lead for the helpers)
 #endif
 #ifndef MPLX_X_EARLY_TOMB
 #define MPLX_X_EARLY_TOMB 0   // (A/B, off) TBL_DEAD_ID of an abandoned claim stored ahead of the parallel commit instead of behind it
@@ -754,12 +757,12 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
             S.any_shared = 0;
             S.dep_cause = 0;
             if constexpr (HELP) {
-              // announce the wish list written during the batch that just ended (complete: a __syncthreads() lies
-              // between); the expansion count is the helpers' hint for choosing whom to serve (one batch old here)
+              // the expansion count is the helpers' hint for choosing whom to serve (one batch old here); the wish list of the
+              // batch that just ended was announced when it was written (MPLX_X_WISH_NOW; without it: here, a batch late)
               if (S.helped && S.box_seq) {
                 HelpBox *box = P.boxes + blockIdx.x;
                 st_u64(&box->n_expanded, n_expanded_now);
-                st_u64(&box->seq, ((unsigned long long)P.epoch << 32) | (S.box_seq + 1ull));
+                if (!MPLX_X_WISH_NOW) st_u64(&box->seq, ((unsigned long long)P.epoch << 32) | (S.box_seq + 1ull));
               }
             }
           }
@@ -871,10 +874,10 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
               }
             }
 #endif
-            // announce the wish list written during the previous batch (complete: a __syncthreads() lies between)
+            // (without MPLX_X_WISH_NOW: announce the wish list written during the previous batch)
             if (S.helped && S.box_seq) {
               st_u64(&box->n_expanded, S.c_expanded);
-              st_u64(&box->seq, ((unsigned long long)P.epoch << 32) | (S.box_seq + 1ull));
+              if (!MPLX_X_WISH_NOW) st_u64(&box->seq, ((unsigned long long)P.epoch << 32) | (S.box_seq + 1ull));
             }
             if ((S.cyc[7] & 7ull) == 1ull) S.helped = ld_u32(&box->helpers) != 0u;
           }
@@ -1068,12 +1071,19 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
           MPLX_T2(S, 19, t3);
           if constexpr (HELP) {
             // wish list: the front of what is left of OPEN (sorted) = the candidates of the next batches.  Announced
-            // by the seq store at the start of the NEXT batch, so no wait for these stores is needed here.
+            // by the seq store right behind it (MPLX_X_WISH_NOW; the same wave, no wait in between): its first sixteen
+            // entries are the likely candidates of the NEXT batch, and an announcement left to that batch's set-up
+            // reached the helpers when those entries were being selected -- every state that pops two batches after its
+            // creation missed its look-ahead record by construction.  A helper that sees the seq ahead of some of the list's
+            // words reads the list of two batches ago in their place: records of this query, most of them served (performance only).
             if (S.helped && tid < WISH) {
               unsigned long long v = ~0ull;
               if ((uint32_t)tid < n - kc) v = ((unsigned long long)((uint32_t)q & 0xFFFFu) << 48) | (unsigned long long)Q.node_rec(S.near_id[tid]);
               st_u64(&(P.boxes + blockIdx.x)->wish[S.box_seq & 1ull][opaque(tid)], v);
-              if (tid == 0) S.box_seq++;
+              if (tid == 0) {
+                S.box_seq++;
+                if (MPLX_X_WISH_NOW) st_u64(&(P.boxes + blockIdx.x)->seq, ((unsigned long long)P.epoch << 32) | (S.box_seq + 1ull));
+              }
             }
           }
         }
