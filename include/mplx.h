@@ -225,6 +225,9 @@ int mplx_set_helpers(mplx_ctx *ctx, int32_t per_leader, int32_t reserved, uint64
 /* last batch: [0] heuristic-cache rows used, [1] queries finished, [2] helpers that gave up on a leader that
  * completed no batch for ~1 s of polling (0 in a healthy run), [3] helpers that left because every running leader was served */
 int mplx_helper_stats(const mplx_ctx *ctx, uint32_t stats[4]);
+/* last batch: successor records the helpers loaded one word of, ahead of the leader's table look-up (speculative kernels with
+ * lattices of at most 31 inputs; a diagnostic: the touch changes no result) */
+int mplx_helper_touches(const mplx_ctx *ctx, uint32_t *touches);
 /* f-width of one coarse OPEN bucket; the fine level divides it by 1024.  0 = default: 3*w*dt for searches on the speculative kernels with
  * lattices of at most 64 inputs, 0.5*w*dt for their larger lattices, 8*w*dt on the one-node kernels, 64*w*dt for LPA*.  A speed knob only: the
  * pop order -- and with it every result -- does not depend on it (tests/test_gpu_scale.py). */

@@ -96,7 +96,7 @@ struct mplx_ctx {
   uint32_t help_epoch = 0;
   unsigned long long help_done_init = 0;
   HelpBox *dbg_boxes = nullptr;
-  uint32_t help_stats[4] = {0, 0, 0, 0};
+  uint32_t help_stats[5] = {0, 0, 0, 0, 0};  // ([4]: record touches of the helpers, mplx_helper_touches)
   uint32_t help_ctr_back[HELP_CTR_WORDS] = {};
   bool help_stats_pending = false;  // last batch: cache rows used, queries done, helpers that gave up on a stopped leader, helpers that found every leader served
   // streamed batches (mplx_plan_batch_submit / _wait): the batch launched on this context's stream and not yet collected.
@@ -773,6 +773,7 @@ extern "C" int mplx_helper_stats(const mplx_ctx *cc, uint32_t stats[4]) {
     c->help_stats[1] = c->help_ctr_back[32];
     c->help_stats[2] = c->help_ctr_back[2];
     c->help_stats[3] = c->help_ctr_back[3];
+    c->help_stats[4] = c->help_ctr_back[5];
     c->help_stats_pending = false;
 #ifdef MPLX_HELP_DEBUG
     {
@@ -794,6 +795,13 @@ extern "C" int mplx_helper_stats(const mplx_ctx *cc, uint32_t stats[4]) {
   }
   for (int i = 0; i < 4; i++) stats[i] = c->help_stats[i];
   return MPLX_OK;
+}
+extern "C" int mplx_helper_touches(const mplx_ctx *cc, uint32_t *touches) {
+  uint32_t st[4];
+  if (!touches) return MPLX_ERR_ARG;
+  const int rc = mplx_helper_stats(cc, st);  // (takes in the read-back of the last batch)
+  if (rc == MPLX_OK) *touches = cc->help_stats[4];
+  return rc;
 }
 extern "C" int mplx_set_record(mplx_ctx *c, uint32_t cap) {
   if (!c) return MPLX_ERR_ARG;

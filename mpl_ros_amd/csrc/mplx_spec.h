@@ -67,6 +67,10 @@
 #define MPLX_X_PROBE2 1       // (round 6) the look-up's first load brings the home slot AND its neighbour (almost always the same 64-byte line): a
                               // key whose home slot is taken by another state no longer costs the slowest lane of the batch a second dependent trip
 #endif
+#ifndef MPLX_X_HELP_TOUCH
+#define MPLX_X_HELP_TOUCH 1   // (HELP builds, units of 32 lanes) a helper loads the table slot and one word of the record of every successor it
+                              // finds: the lines are on their way to the memory-side cache when the leader looks the successor up (helper_serve)
+#endif
 
 namespace mplx {
 
@@ -385,6 +389,9 @@ __device__ __forceinline__ void helper_serve(const SearchParams &P, SM &S, int t
   const uint32_t q = (uint32_t)S.help_q;
   const uint32_t epoch = P.epoch;
   unsigned long long last_seq = ((unsigned long long)epoch << 32) | 1ull;
+  // MPLX_X_HELP_TOUCH: the word a record touch loaded (never looked at: consumed by an empty asm statement where the next group
+  // waits for its node's state anyway), and this lane's count of touches (diagnostics: cache_next[5])
+  [[maybe_unused]] uint32_t touch_word = 0, n_touch = 0;
   for (;;) {
     if (tid == 0) {
       unsigned long long seq;
@@ -412,7 +419,14 @@ __device__ __forceinline__ void helper_serve(const SearchParams &P, SM &S, int t
       S.help_seq = seq;
     }
     __syncthreads();
-    if (!S.help_go) break;
+    if (!S.help_go) {
+      if constexpr (MPLX_X_HELP_TOUCH && UL == 32) {  // (every lane is here: the wave's touches in one add)
+        asm volatile("" ::"v"(touch_word));
+        const uint32_t wt = wave_incl_sum<64>(n_touch);
+        if ((tid & 63) == 63 && wt) atomicAdd(P.cache_next + 5, wt);
+      }
+      break;
+    }
     last_seq = S.help_seq;
     // ---- the announced list -> the entries that are mine and still missing
     if (tid < WISH) {
@@ -448,7 +462,21 @@ __device__ __forceinline__ void helper_serve(const SearchParams &P, SM &S, int t
       }
       unit_sync<UL>();
       LaneSucc L;
-      expand_unit<UL, BLOCK, CONTROL>(P, S, tid, live, L);
+      // MPLX_X_HELP_TOUCH: the home slot of the successor in the served query's part of the state table -- the position the leader's
+      // look-up will compute -- asked for as soon as the key exists; it travels during the sampling, and nothing waits for it before
+      // the row and the record are published
+      [[maybe_unused]] unsigned long long t_h64 = 0, t_v0 = TBL_EMPTY;
+      if constexpr (MPLX_X_HELP_TOUCH && UL == 32) {
+        asm volatile("" ::"v"(touch_word));  // (the previous group's touch: this wave has just waited for its node's state, issued later)
+        expand_unit<UL, BLOCK, CONTROL>(P, S, tid, live, L, [&](const LaneSucc &l) {
+          if (l.valid && !l.blocked) {
+            t_h64 = key_hash64(l.key, nk);
+            t_v0 = ld_u64_probe(&P.table[(size_t)(t_h64 ^ ((unsigned long long)q * 0x9E3779B97F4A7C15ull)) & (size_t)P.table_mask]);
+          }
+        });
+      } else {
+        expand_unit<UL, BLOCK, CONTROL>(P, S, tid, live, L);
+      }
       const bool act = L.valid && !L.blocked;
       double h = 0.0;
       if (act && P.eps != 0.0) h = get_heur(S.hp, CONTROL, L.tn, L.key, nk);
@@ -504,6 +532,26 @@ __device__ __forceinline__ void helper_serve(const SearchParams &P, SM &S, int t
         unsigned long long *cr = (unsigned long long *)&P.cache_c[rec];
         st_u64(cr + 1, ((unsigned long long)bmask << 32) | (unsigned long long)(vmask | CACHE_READY));
         st_u64(cr, ((unsigned long long)(uint32_t)key_hash64(S.cur_key[ku], nk) << 32) | (unsigned long long)rp1);
+      }
+      if constexpr (MPLX_X_HELP_TOUCH && UL == 32) {
+        // Record touch (performance only): where the home slot names a state of the served query, one word of that
+        // state's record is loaded, so that the record's hot line is in the memory-side cache when the leader's look-up asks for
+        // it one to three batches from now.  No second probe step: a successor that lost its home slot is simply not warmed.
+        // Everything read on the way -- the slot, the chunk entry -- may be stale or torn (a claim being resolved, an entry of the
+        // previous launch, a chunk handed back and taken by another query) and is used for nothing but the address; the loaded word
+        // is never looked at.  The address is inside the node pool whatever they hold: the chunk index is below MAX_NODE_CH (the
+        // row of the chunk table has that many words), the touch is skipped unless the chunk entry is below P.node_chunks, and the
+        // pool holds P.node_chunks << NODE_CH_LOG records.  (A touch can bring a record's line into this XCD's L2 before the
+        // state doubles on it have landed; a later read of that state for a wish-list entry then gives another key hash and the
+        // leader refuses the entry -- a missed hit, the rule of every late read of a node state.)
+        const uint32_t id = (uint32_t)t_v0;
+        if (act && id < CLAIM_BASE && (t_v0 & 0xFFFFFFFF00000000ull) == tbl_tagq(t_h64, q, P.tbl_epoch) && (id >> NODE_CH_LOG) < (uint32_t)MAX_NODE_CH) {
+          const uint32_t ch = ld_u32(&P.node_tables[(size_t)q * MAX_NODE_CH + (id >> NODE_CH_LOG)]);
+          if (ch < P.node_chunks) {
+            touch_word = ld_u32((const uint32_t *)(P.node_pool + (((size_t)ch << NODE_CH_LOG) + (id & ((1u << NODE_CH_LOG) - 1u))) * rec_bytes(CONTROL)));
+            n_touch++;
+          }
+        }
       }
       if (lu == 0) S.hc_row[ku] = 0;
       __syncthreads();
@@ -769,9 +817,15 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
           // chunk capacity for everything the batch can create: one pool per wave
           const uint32_t room = (uint32_t)(K * P.n_u + K);
           bool ok;
-          if (tid == 64)
+          if (tid == 64) {
+            [[maybe_unused]] const uint32_t had = batch_no ? S.node_chunks : 0u;  // (the first chunk is taken by query_reset)
             ok = Q.ensure_nodes(S.n_nodes + room);
-          else if (tid == 128)
+            // MPLX_X_HELP_TOUCH: the query's chunk table in memory follows the one in LDS while the search runs (it used to be written
+            // at the end of the query only: publish_chunk_tables, which stays), for the helpers' record touches -- posted stores,
+            // off the chain; an entry a helper does not see yet fails its bounds check or warms a harmless line
+            if constexpr (HELP && MPLX_X_HELP_TOUCH && UL == 32)
+              for (uint32_t ch = had; ch < S.node_chunks; ch++) st_u32(&P.node_tables[(size_t)q * MAX_NODE_CH + ch], Q.node_chunk(ch));
+          } else if (tid == 128)
             ok = Q.ensure_edges(S.n_edges + room);
           else
             ok = Q.ensure_open(S.n_log + room);
@@ -885,9 +939,12 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
         if ((tid & 63) == 0 && tid < 192) {  // chunk capacity for everything this batch can create: one pool per wave
           const uint32_t room = (uint32_t)(K * P.n_u + K);
           bool ok;
-          if (tid == 0)
+          if (tid == 0) {
+            [[maybe_unused]] const uint32_t had = batch_no > 1u ? S.node_chunks : 0u;
             ok = Q.ensure_nodes(S.n_nodes + room);
-          else if (tid == 64)
+            if constexpr (HELP && MPLX_X_HELP_TOUCH && UL == 32)  // (the chunk table in memory follows the one in LDS: batch_setup above)
+              for (uint32_t ch = had; ch < S.node_chunks; ch++) st_u32(&P.node_tables[(size_t)q * MAX_NODE_CH + ch], Q.node_chunk(ch));
+          } else if (tid == 64)
             ok = Q.ensure_edges(S.n_edges + room);
           else
             ok = Q.ensure_open(S.n_log + room);
@@ -1798,7 +1855,10 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
       }, SpecCounts{{S.c_cand, S.c_cand - S.c_live, S.c_live, S.c_cut}}, t_begin, ld_state);
       P.out[q].n_refill |= (unsigned long long)S.c_drop << 32;  // (QueryOut: the high word; query_refills / query_open_dropped)
 #ifdef MPLX_LOOKUP_TIMERS
-      if (P.nq == 1 || q % 61 == 0) {  // (a batch: a sample of its queries -- a thousand workgroups printing at once tear each other's lines)
+#ifndef MPLX_TIMERS_PRINT_BATCHES
+#define MPLX_TIMERS_PRINT_BATCHES (~0ull)  // (-DMPLX_TIMERS_PRINT_BATCHES=100000: the long queries of a batch print as well -- query 1005 of the C4 batch)
+#endif
+      if (P.nq == 1 || q % 61 == 0 || S.cyc[7] >= MPLX_TIMERS_PRINT_BATCHES) {  // (a batch: a sample of its queries -- a thousand workgroups printing at once tear each other's lines)
       printf("cyc2 q%d batches %llu:", q, S.cyc[7]);
       for (int i = 0; i < 24; i++) printf(" %llu", S.cyc2[i] / (S.cyc[7] ? S.cyc[7] : 1ull));
       printf("\n  max-over-lanes: heuristic done %llu, barrier arrival %llu\n", S.sum_heur / S.cyc[7], S.sum_arr / S.cyc[7]);

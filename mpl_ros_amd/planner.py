@@ -616,6 +616,13 @@ class VoxelMapPlanner:
         ctx.check(ctx.lib.mplx_helper_stats(ctx.h, st))
         return dict(zip(("cache_rows_used", "queries_done", "helpers_gave_up", "helpers_surplus"), [int(x) for x in st]))
 
+    def helperTouches(self):
+        """successor records the helpers of the last batch loaded ahead of the leader's look-up (a diagnostic)"""
+        ctx = self._ctx()
+        n = C.c_uint32()
+        ctx.check(ctx.lib.mplx_helper_touches(ctx.h, C.byref(n)))
+        return int(n.value)
+
     def setRecord(self, cap):
         ctx = self._ctx()
         ctx.check(ctx.lib.mplx_set_record(ctx.h, int(cap)))

@@ -73,7 +73,7 @@ def main():
             if it:
                 ms.append(pl.lastKernelMs())
         out[mode] = {"kernel_ms": [round(x, 2) for x in ms], "min_ms": round(min(ms), 2), "mean_ms": round(sum(ms) / len(ms), 2), "expansions": n_exp,
-                     "Mexp_per_s": round(n_exp / min(ms) / 1e3, 2), "digests": sorted(digs), "helpers": str(pl.helperStats())}
+                     "Mexp_per_s": round(n_exp / min(ms) / 1e3, 2), "digests": sorted(digs), "helpers": str(pl.helperStats()), "touches": pl.helperTouches()}
         print(json.dumps({mode: out[mode]}), file=sys.stderr, flush=True)
         del mu, pl
     print(json.dumps(out))

@@ -2,6 +2,8 @@
 (tools/build_kernel_variant.sh timers "-DMPLX_ONLY_ACC -DMPLX_LOOKUP_TIMERS -DMPLX_PHASE_TIMERS=1" "help spec").
   run tail   : query 1005 of the C4 stream (the one that runs into the 2 M cap) alone, helpers from the start
   run bulk   : the C4-ACC batch capped at 20 000 expansions per query, no helpers (256 compute units busy, no tail)
+  run block  : the bench's blocking batch (1024 queries, cap 2 000 000, helpers auto); the RUN line is query QI's.  The timers build needs
+               -DMPLX_TIMERS_PRINT_BATCHES=100000 for the long query's cyc2 line; parse with PARSE_Q=1005 to take that query's lines alone
   parse FILE : the kernel's printf lines of one of the above -> mean cycles per batch and section, weighted by batches
 usage: MPLX_LIB=build_tmp/libmplx_timers.so python tools/phase_table.py run tail > tail.txt; python tools/phase_table.py parse tail.txt"""
 import os
@@ -56,7 +58,20 @@ def run(mode):
             pl.plan(util.gpu_wp(s), util.gpu_wp(g))
             r = pl.getResult()
             cy = pl.queryCycles()
-            print(f"RUN tail it {it} query {qi} expansions {r.n_expanded} kernel_ms {pl.lastKernelMs():.1f} batches {cy['batches']} dep {cy['dep_batches']} hits {cy['cache_hits']} expand_cyc {cy['expand']}", flush=True)
+            print(f"RUN tail it {it} query {qi} expansions {r.n_expanded} kernel_ms {pl.lastKernelMs():.1f} batches {cy['batches']} dep {cy['dep_batches']} hits {cy['cache_hits']} expand_cyc {cy['expand']} "
+                  f"touches {pl.helperTouches()}", flush=True)
+    elif mode == "block":
+        qi = int(os.environ.get("QI", "1005"))
+        pools = mapgen.c4_pools(False, 1024, 2_000_000)
+        mu, pl = util.make_gpu(grid, origin, res, U, v_max=2.0, a_max=1.0, tol_pos=0.5, max_expand=2_000_000, n_slots=1024, max_nodes=pools["nodes"], max_edges=pools["edges"], max_log=pools["log"])
+        pl.setDeadline(100.0)
+        starts = [util.gpu_wp(q[0]) for q in queries]
+        goals = [util.gpu_wp(q[1]) for q in queries]
+        for it in range(2):
+            res_ = pl.planBatch(starts, goals)
+            cy = pl.queryCycles(qi)
+            print(f"RUN block it {it} query {qi} expansions {res_[qi].n_expanded} kernel_ms {pl.lastKernelMs():.1f} batches {cy['batches']} dep {cy['dep_batches']} hits {cy['cache_hits']} expand_cyc {cy['expand']} "
+                  f"touches {pl.helperTouches()}", flush=True)
     else:
         cap = int(os.environ.get("CAP", "20000"))
         pools = mapgen.c4_pools(False, 1024, cap)
@@ -78,6 +93,8 @@ def parse(path):
     runs = re.findall(r"RUN \w+ it \d+ [^\n]*", txt)  # (the bulk run's kernel lines may interleave with it mid-line)
     run_line = runs[-1]
     lines = re.findall(r"cyc2 q(\d+) batches (\d+):((?: \d+){24})", txt)
+    if os.environ.get("PARSE_Q"):  # (a batch: the lines of one query)
+        lines = [l for l in lines if l[0] == os.environ["PARSE_Q"]]
     n_it = len(runs)
     lines = lines[len(lines) - len(lines) // max(n_it, 1):]
     body = txt
