@@ -1,5 +1,6 @@
-"""ctypes binding of oracle/_ref/libpolymap_ref.so: the reference's own env_poly_map / PolyMapUtil / collide()
-compiled from where they lie (oracle/ref_stubs/poly_map_ref_api.cpp, `make -C oracle ref`).
+"""ctypes binding of oracle/_ref/libpolymap_ref.so and oracle/_ref/libpolymap3_ref.so: the reference's own env_poly_map /
+PolyMapUtil / collide() compiled from where they lie at Dim = 2 (oracle/ref_stubs/poly_map_ref_api.cpp -> RefWorld) and at
+Dim = 3 (oracle/ref_stubs/poly_map3_ref_api.cpp -> RefWorld3D), `make -C oracle ref`.
 TEST INFRASTRUCTURE ONLY -- see oracle/mpl_oracle.h."""
 import ctypes as C
 import os
@@ -8,10 +9,12 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "_ref", "libpolymap_ref.so")
+LIB3_PATH = os.path.join(_HERE, "_ref", "libpolymap3_ref.so")
 
 
-def available():
-    return os.path.exists(LIB_PATH)
+def available(dim=2):
+    """is the compiled reference of that dimension there?  (2: libpolymap_ref.so, 3: libpolymap3_ref.so)"""
+    return os.path.exists({2: LIB_PATH, 3: LIB3_PATH}[dim])
 
 
 _lib = None
@@ -172,4 +175,112 @@ class RefWorld:
     def node(self, i):
         s = np.zeros(9); g = C.c_double(); h = C.c_double()
         self.L.refpoly_get_node(int(i), s.ctypes.data, C.byref(g), C.byref(h))
+        return s, g.value, h.value
+
+
+_lib3 = None
+
+
+def lib3():
+    global _lib3
+    if _lib3 is None:
+        L = C.CDLL(LIB3_PATH)
+        P, D, I, V = C.c_void_p, C.c_double, C.c_int, C.c_void_p
+        L.refpoly3_create.restype = P
+        L.refpoly3_create.argtypes = [V, V]
+        L.refpoly3_destroy.argtypes = [P]
+        L.refpoly3_set_start_time.argtypes = [P, D]
+        L.refpoly3_add_static.argtypes = [P, I, V, V]
+        L.refpoly3_add_linear.argtypes = [P, I, V, V, V, D]
+        L.refpoly3_add_nonlinear.argtypes = [P, I, V, I, V, I, D, I, I]
+        L.refpoly3_commit.argtypes = [P]
+        L.refpoly3_set_env.argtypes = [P, I, V, D, D, D, D, D]
+        L.refpoly3_is_inside.argtypes = [P, V]
+        L.refpoly3_is_free_point.argtypes = [P, V, D]
+        L.refpoly3_get_succ.argtypes = [P, V, I, V, V, V]
+        L.refpoly3_plan.argtypes = [P, V, V, I, D, D, I, I]
+        L.refpoly3_traj_cost.restype = D
+        L.refpoly3_set_heuristic.argtypes = [V, V]
+        L.refpoly3_get_expanded.argtypes = [V]
+        L.refpoly3_get_traj.argtypes = [V, V]
+        L.refpoly3_get_node.argtypes = [I, V, C.POINTER(D), C.POINTER(D)]
+        _lib3 = L
+    return _lib3
+
+
+def _a(x):
+    return np.ascontiguousarray(x, dtype=np.float64)
+
+
+class RefWorld3D:
+    """One reference PolyMapUtil<3> + env_poly_map<3>, filled from a mpl_ros_amd.poly_map3d.PolyWorld3D.  The interface of
+    tests/poly_checker.CheckerWorld: get_succ, plan, node; rows are the 3-D layouts (hyperplanes {p3, n3}, segments
+    {cx[6], cy[6], cz[6], T}, states pos3 vel3 acc3 jrk3 t)."""
+
+    def __init__(self, world, control, U, dt, v_max=-1.0, a_max=-1.0, j_max=-1.0, w=10.0):
+        L = lib3()
+        self.L, self.control = L, int(control)
+        self.h = L.refpoly3_create(_a(world.ori).ctypes.data, _a(world.dim).ctypes.data)
+        L.refpoly3_set_start_time(self.h, world.start_t)
+        for o in world.static:
+            L.refpoly3_add_static(self.h, len(o.poly), o.poly.ctypes.data, _a(o.p).ctypes.data)
+        for o in world.linear:
+            L.refpoly3_add_linear(self.h, len(o.poly), o.poly.ctypes.data, _a(o.p).ctypes.data, _a(o.v).ctypes.data, o.cov_v)
+        for o in world.nonlinear:
+            L.refpoly3_add_nonlinear(self.h, len(o.poly), o.poly.ctypes.data, len(o.segs), o.segs.ctypes.data, self.control, o.start_t,
+                                     int(o.disappear_front), int(o.disappear_back))
+        L.refpoly3_commit(self.h)
+        self.U = _a(U).reshape(-1, 3)
+        self.env_kw = dict(dt=float(dt), v_max=float(v_max), a_max=float(a_max), j_max=float(j_max), w=float(w))
+        L.refpoly3_set_env(self.h, len(self.U), self.U.ctypes.data, float(dt), float(v_max), float(a_max), float(j_max), float(w))
+
+    def __del__(self):
+        try:
+            self.L.refpoly3_destroy(self.h)
+        except Exception:
+            pass
+
+    def is_inside(self, pt):
+        return bool(self.L.refpoly3_is_inside(self.h, _a(pt).ctypes.data))
+
+    def is_free(self, pt, t):
+        """PolyMapUtil::isFree(pt, t)"""
+        return bool(self.L.refpoly3_is_free_point(self.h, _a(pt).ctypes.data, float(t)))
+
+    def get_succ(self, state):
+        s = _a(state)
+        n = len(self.U)
+        succ = np.zeros((n, 13)); cost = np.zeros(n); act = np.zeros(n, dtype=np.int32)
+        k = self.L.refpoly3_get_succ(self.h, s.ctypes.data, self.control, succ.ctypes.data, cost.ctypes.data, act.ctypes.data)
+        return succ[:k], cost[:k], act[:k]
+
+    def plan(self, start, goal, eps=1.0, tol_pos=0.5, max_expand=-1, heur_ignore_dynamics=True):
+        """RefWorld.plan at three dimensions: the dynamics-aware heuristic is the CPU oracle's orc_heuristic, handed over with
+        refpoly3_set_heuristic"""
+        s, g = _a(start), _a(goal)
+        keep = None
+        if not heur_ignore_dynamics:
+            from . import orc
+            keep = orc.Planner()
+            keep.set_config(self.control, self.U, dt=self.env_kw["dt"], v_max=self.env_kw["v_max"], a_max=self.env_kw["a_max"], j_max=self.env_kw["j_max"],
+                            w=self.env_kw["w"], eps=eps, tol_pos=tol_pos, heur_ignore_dynamics=False)
+            gw = orc.Waypoint()
+            for i in range(3):
+                gw.pos[i], gw.vel[i], gw.acc[i] = g[i], g[3 + i], g[6 + i]
+            gw.control = self.control
+            keep.set_goal(gw)
+            self.L.refpoly3_set_heuristic(C.cast(keep.L.orc_heuristic, C.c_void_p), keep.h)
+        st = self.L.refpoly3_plan(self.h, s.ctypes.data, g.ctypes.data, self.control, float(eps), float(tol_pos), int(max_expand), 1 if heur_ignore_dynamics else 0)
+        del keep
+        ne, nl = self.L.refpoly3_num_expanded(), self.L.refpoly3_traj_len()
+        ids = np.zeros(max(ne, 1), dtype=np.int32)
+        self.L.refpoly3_get_expanded(ids.ctypes.data)
+        tn = np.zeros(nl + 1, dtype=np.int32); ta = np.zeros(max(nl, 1), dtype=np.int32)
+        if st == 0 and nl:
+            self.L.refpoly3_get_traj(tn.ctypes.data, ta.ctypes.data)
+        return dict(status=st, expanded=ids[:ne], n_nodes=self.L.refpoly3_num_nodes(), cost=self.L.refpoly3_traj_cost(), actions=ta[:nl], node_ids=tn[:nl + 1] if nl else tn[:0])
+
+    def node(self, i):
+        s = np.zeros(13); g = C.c_double(); h = C.c_double()
+        self.L.refpoly3_get_node(int(i), s.ctypes.data, C.byref(g), C.byref(h))
         return s, g.value, h.value

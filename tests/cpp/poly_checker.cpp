@@ -234,6 +234,8 @@ struct Base {
   virtual void add(int kind, int n_hp, const double *hp, const double *p, const double *v, double cov_v, int n_seg, const double *segs, int control, double start_t, int df, int db) = 0;
   virtual void set_env(int n_u, const double *U, double dt, double v_max, double a_max, double j_max, double w) = 0;
   virtual int get_succ(const double *state, int control, double *succ, double *cost, int *action) = 0;
+  virtual bool is_inside(const double *pt) const = 0;
+  virtual bool is_free_point(const double *pt, double t) const = 0;
   virtual int plan(const double *start, const double *goal, int control, double eps, double tol_pos, double tol_vel, int max_expand, int heur_mode) = 0;
   // results of the last plan
   std::vector<int> expanded, traj_nodes, traj_act;
@@ -308,6 +310,13 @@ struct Checker : Base {
     for (size_t i = 0; i < s.size(); i++) { to(s[i], succ + (4 * Dim + 1) * i); cost[i] = c[i]; action[i] = a[i]; }
     return (int)s.size();
   }
+  static Vecf<Dim> point(const double *x) {
+    Vecf<Dim> p;
+    for (int i = 0; i < Dim; i++) p(i) = x[i];
+    return p;
+  }
+  bool is_inside(const double *pt) const override { return E.is_inside(point(pt)); }
+  bool is_free_point(const double *pt, double t) const override { return E.is_free(point(pt), t); }
   double linf(const Waypoint<Dim> &x, const Waypoint<Dim> &g) const {
     double d = 0;
     for (int i = 0; i < Dim; i++) d = std::max(d, std::fabs(x.pos(i) - g.pos(i)));
@@ -442,6 +451,9 @@ void pc_add_nonlinear(void *h, int n_hp, const double *hp, int n_seg, const doub
 void pc_set_env(void *h, int n_u, const double *U, double dt, double v_max, double a_max, double j_max, double w) { ((Base *)h)->set_env(n_u, U, dt, v_max, a_max, j_max, w); }
 // state: pos vel acc jrk (Dim each) t; succ: n_u x (4 Dim + 1); returns the number emitted
 int pc_get_succ(void *h, const double *state, int control, double *succ, double *cost, int *action) { return ((Base *)h)->get_succ(state, control, succ, cost, action); }
+// PolyMapUtil::isInside(pt) and isFree(pt, t); pt: Dim doubles
+int pc_is_inside(void *h, const double *pt) { return ((Base *)h)->is_inside(pt) ? 1 : 0; }
+int pc_is_free_point(void *h, const double *pt, double t) { return ((Base *)h)->is_free_point(pt, t) ? 1 : 0; }
 void pc_set_heuristic(void *fn, const void *planner) { g_heur_fn = (orc_heur_fn)fn; g_heur_planner = planner; }
 int pc_plan(void *h, const double *start, const double *goal, int control, double eps, double tol_pos, double tol_vel, int max_expand, int heur_mode) {
   return ((Base *)h)->plan(start, goal, control, eps, tol_pos, tol_vel, max_expand, heur_mode);

@@ -30,6 +30,8 @@ def lib():
         L.pc_add_nonlinear.argtypes = [P, I, V, I, V, I, D, I, I]
         L.pc_set_env.argtypes = [P, I, V, D, D, D, D, D]
         L.pc_get_succ.argtypes = [P, V, I, V, V, V]
+        L.pc_is_inside.argtypes = [P, V]
+        L.pc_is_free_point.argtypes = [P, V, D]
         L.pc_set_heuristic.argtypes = [V, V]
         L.pc_plan.argtypes = [P, V, V, I, D, D, D, I, I]
         for n in ("pc_num_expanded", "pc_num_nodes", "pc_traj_len"):
@@ -79,6 +81,13 @@ class CheckerWorld:
     @property
     def ns(self):
         return 4 * self.dim + 1
+
+    def is_inside(self, pt):
+        return bool(self.L.pc_is_inside(self.h, _a(pt).ctypes.data))
+
+    def is_free(self, pt, t):
+        """PolyMapUtil::isFree(pt, t)"""
+        return bool(self.L.pc_is_free_point(self.h, _a(pt).ctypes.data, float(t)))
 
     def get_succ(self, state):
         s = _a(state)

@@ -15,7 +15,7 @@ from tests import poly_checker as pc
 from tests import poly_scenes as ps
 from tests.poly_compare import compare_get_succ, compare_plans
 
-needs_ref = pytest.mark.skipif(not refpoly.available(), reason="oracle/_ref/libpolymap_ref.so not built (make -C oracle ref)")
+needs_ref = pytest.mark.skipif(not refpoly.available(), reason="oracle/_ref/libpolymap_ref.so (Dim = 2; Dim = 3 is libpolymap3_ref.so) not built (make -C oracle ref)")
 ACC, JRK, VEL, SNP = pm.ACC, pm.JRK, pm.VEL, pm.SNP
 NAMES = list(ps.SCENES)
 CTRL_NAME = {ACC: "acc", JRK: "jrk", VEL: "vel", SNP: "snp"}

@@ -11,7 +11,7 @@ from mpl_ros_amd import poly_map as pm
 from oracle import refpoly
 from tests.poly_compare import compare_get_succ as _compare_get_succ, compare_plans as _compare_plans  # (shared with test_poly_geometry.py)
 
-needs_ref = pytest.mark.skipif(not refpoly.available(), reason="oracle/_ref/libpolymap_ref.so not built (make -C oracle ref)")
+needs_ref = pytest.mark.skipif(not refpoly.available(), reason="oracle/_ref/libpolymap_ref.so (Dim = 2; Dim = 3 is libpolymap3_ref.so) not built (make -C oracle ref)")
 
 U9, acc_segs = pm.U9, pm.acc_segs
 

@@ -1,8 +1,10 @@
 """3-D moving-obstacle planner (PolyMapPlanner3D): mplx_poly3_* against the CPU checker tests/cpp/poly_checker.cpp.
 
 The checker restates env_poly_map / PolyMapUtil / collide() / the obstacle classes templated on Dim.  CPU: at Dim = 2 it agrees
-bit for bit with oracle/_ref/libpolymap_ref.so (the reference's own headers compiled) on get_succ and on whole plans -- only
-then is it trusted at Dim = 3.  -m gpu: the HIP kernels against it at Dim = 3, bit-exact."""
+bit for bit with oracle/_ref/libpolymap_ref.so (the reference's own headers compiled) on get_succ and on whole plans, and at
+Dim = 3 with oracle/_ref/libpolymap3_ref.so (the same headers instantiated at three dimensions) on the worlds of this file; the
+named 3-D scenes are in tests/test_poly3_geometry.py.  -m gpu: the HIP kernels against the checker at Dim = 3, bit-exact (the
+comparison bodies are those of tests/poly_compare.py)."""
 import ctypes as C
 
 import numpy as np
@@ -13,9 +15,11 @@ from mpl_ros_amd import poly_map as pm
 from mpl_ros_amd import poly_map3d as p3
 from oracle import refpoly
 from tests import poly_checker as pc
+from tests.poly_compare import compare_get_succ, compare_plans, same_plan as _same_plan, same_succ as _same_succ
 from tests.test_poly_map import random_states, random_states_general, random_world, random_world_general
 
-needs_ref = pytest.mark.skipif(not refpoly.available(), reason="oracle/_ref/libpolymap_ref.so not built (make -C oracle ref)")
+needs_ref = pytest.mark.skipif(not refpoly.available(), reason="oracle/_ref/libpolymap_ref.so (Dim = 2; Dim = 3 is libpolymap3_ref.so) not built (make -C oracle ref)")
+needs_ref3 = pytest.mark.skipif(not refpoly.available(3), reason="oracle/_ref/libpolymap3_ref.so (Dim = 3; Dim = 2 is libpolymap_ref.so) not built (make -C oracle ref)")
 
 U9 = pm.U9
 
@@ -38,15 +42,6 @@ def test_no_gpu_means_loud_failure():
         p3.PolyTeam3D()
 
 
-def _same_succ(a, b):
-    (sa, ca, aa), (sb, cb, ab) = a, b
-    assert np.array_equal(aa, ab)
-    assert np.array_equal(sa, sb)  # bit-exact f64 (array_equal: -0.0 == 0.0, the sign is checked below)
-    assert np.array_equal(np.signbit(sa), np.signbit(sb))
-    assert all(x == y or (np.isinf(x) and np.isinf(y)) for x, y in zip(ca, cb))
-    return int(np.isinf(ca).sum()), int(np.isfinite(ca).sum())
-
-
 @needs_ref
 @pytest.mark.parametrize("control", [pm.ACC, pm.JRK])
 def test_checker_at_dim2_equals_the_compiled_reference_get_succ(control):
@@ -66,15 +61,6 @@ def test_checker_at_dim2_equals_the_compiled_reference_get_succ(control):
             i, f = _same_succ(b, a)
             n_inf += i; n_fin += f
     assert n_inf > 100 and n_fin > 500
-
-
-def _same_plan(a, b, ref, chk, cols):
-    assert a["status"] == b["status"]
-    assert np.array_equal(a["expanded"], b["expanded"]) and a["n_nodes"] == b["n_nodes"]
-    assert a["cost"] == b["cost"] or (np.isinf(a["cost"]) and np.isinf(b["cost"]))
-    assert np.array_equal(a["actions"], b["actions"]) and np.array_equal(a["node_ids"], b["node_ids"])
-    for nid in a["node_ids"]:
-        assert np.array_equal(ref.node(int(nid))[0][cols], chk.node(int(nid))[0][cols])
 
 
 @needs_ref
@@ -158,31 +144,56 @@ def _u27():
     return p3.control_lattice(1.0, 1)
 
 
+SUCC_SETUPS = [(pm.ACC, False), (pm.ACC, True), (pm.JRK, True), (pm.VEL, False)]  # (control, cubic obstacle trajectories) of the GPU test below
+
+
+def succ_case(control, jrk_obstacles):
+    """the worlds and states test_get_succ_batch_equals_the_checker runs on"""
+    rng = np.random.default_rng(1000 + 10 * control + int(jrk_obstacles))
+    worlds = [random_world3d(rng, jrk_obstacles) for _ in range(4)]
+    K = 160
+    world_of = np.repeat(np.arange(len(worlds)), K // len(worlds))
+    states = np.concatenate([random_states3d(rng, W, K // len(worlds), control) for W in worlds])  # (faces, outside, inside an obstacle)
+    return worlds, world_of, states
+
+
+@needs_ref3
+@pytest.mark.parametrize("control,jrk_obstacles", SUCC_SETUPS + [(pm.SNP, True)])
+def test_checker_at_dim3_equals_the_compiled_reference_get_succ(control, jrk_obstacles):
+    """the very worlds and states of the GPU comparison below (one of them again off the origin), and SNP on top"""
+    worlds, world_of, states = succ_case(control, jrk_obstacles)
+    far = p3.PolyWorld3D(worlds[0].ori + (-103.7, 41.3, 12.5), worlds[0].dim, worlds[0].start_t)
+    shift = np.array([-103.7, 41.3, 12.5])
+    far.static = [p3.StaticObstacle3D(o.poly, o.p + shift) for o in worlds[0].static]
+    far.linear = [p3.LinearObstacle3D(o.poly, o.p + shift, o.v, o.cov_v) for o in worlds[0].linear]
+    for o in worlds[0].nonlinear:
+        sg = o.segs.copy()
+        sg[:, [5, 11, 17]] += shift
+        far.nonlinear.append(p3.NonlinearObstacle3D(o.poly, sg, o.start_t, o.disappear_front, o.disappear_back))
+    moved = states[world_of == 0].copy()
+    moved[:, 0:3] += shift
+    if control == pm.SNP:
+        states[:, 9:12] = np.round(np.random.default_rng(7).uniform(-1, 1, (len(states), 3)), 1)
+    n_inf = n_fin = 0
+    for W, ss in [(W, states[world_of == k]) for k, W in enumerate(worlds)] + [(far, moved)]:
+        ref, chk = refpoly.RefWorld3D(W, control, _u27(), **KW3), pc.CheckerWorld(W, control, _u27(), **KW3)
+        for s in ss:
+            i, f = _same_succ(chk.get_succ(s), ref.get_succ(s))
+            n_inf += i; n_fin += f
+    assert n_fin > 300 and n_inf > 100
+
+
 # ---------------------------------------------------------------- GPU
 @pytest.mark.gpu
-@pytest.mark.parametrize("control,jrk_obstacles", [(pm.ACC, False), (pm.ACC, True), (pm.JRK, True), (pm.VEL, False)])
+@pytest.mark.parametrize("control,jrk_obstacles", SUCC_SETUPS)
 def test_get_succ_batch_equals_the_checker(control, jrk_obstacles):
-    rng = np.random.default_rng(1000 + 10 * control + int(jrk_obstacles))
     U = _u27()
-    worlds = [random_world3d(rng, jrk_obstacles) for _ in range(4)]
+    worlds, world_of, states = succ_case(control, jrk_obstacles)
     team = p3.PolyTeam3D()
     team.configure(control, U, **KW3)
     team.set_worlds(worlds)
     chks = [pc.CheckerWorld(W, control, U, **KW3) for W in worlds]
-    K = 160
-    world_of = np.repeat(np.arange(len(worlds)), K // len(worlds))
-    states = np.concatenate([random_states3d(rng, W, K // len(worlds), control) for W in worlds])  # (faces, outside, inside an obstacle)
-    out = team.get_succ_batch(world_of, states)
-    n_u, n_inf, n_fin = len(U), 0, 0
-    for k in range(K):
-        succ, cost, act = chks[world_of[k]].get_succ(states[k])
-        got = [out[k * n_u + i] for i in range(n_u) if out[k * n_u + i].valid]
-        assert [g.action for g in got] == act.tolist(), k
-        for g, so, co in zip(got, succ, cost):
-            gs = np.array(g.state[:])
-            assert np.array_equal(gs, so) and np.array_equal(np.signbit(gs), np.signbit(so)), (k, g.action)
-            assert g.cost == co or (np.isinf(g.cost) and np.isinf(co)), (k, g.action, g.cost, co)
-            n_inf += int(np.isinf(co)); n_fin += int(np.isfinite(co))
+    n_fin, n_inf = compare_get_succ(team, worlds, chks, world_of, states, len(U), signs=True)
     assert n_fin > 300 and n_inf > 100
 
 
@@ -197,28 +208,7 @@ def _plan_cases(rng, n, control, cubic_obstacles=True):
 
 
 def _compare_plans(team, chks, world_of, starts, goals, control, **kw):
-    cols = list(range(9)) + [12] if control == pm.JRK else list(range(6)) + [12]
-    team.set_record(1 << 16)
-    R = team.plan_batch(world_of, starts, goals, **kw)
-    n_ok = 0
-    for k, w in enumerate(world_of):
-        ref = chks[w].plan(starts[k], goals[k], eps=kw.get("eps", 1.0), tol_pos=kw.get("tol_pos", 0.5), max_expand=kw.get("max_expand", -1),
-                           heur_ignore_dynamics=kw.get("heur_ignore_dynamics", True), tol_vel=kw.get("tol_vel", -1.0))
-        r = R[k]
-        assert r.status == ref["status"], (k, r.status, ref["status"])
-        assert r.n_expanded == len(ref["expanded"]) and r.n_nodes == ref["n_nodes"], (k, r.n_expanded, len(ref["expanded"]), r.n_nodes, ref["n_nodes"])
-        assert np.array_equal(team.expanded_ids(k), ref["expanded"]), k
-        if ref["status"] == 0:
-            n_ok += 1
-            assert r.cost == ref["cost"], (k, r.cost, ref["cost"])
-            act, ids, st = team.traj(k)
-            assert np.array_equal(act, ref["actions"]) and np.array_equal(ids, ref["node_ids"]), k
-            for i, nid in enumerate(ids):
-                s = chks[w].node(int(nid))[0]
-                assert np.array_equal(st[i][cols], s[cols]), (k, i)
-        else:
-            assert np.isinf(r.cost)
-    return R, n_ok
+    return compare_plans(team, chks, world_of, starts, goals, compare_acc=control == pm.JRK, dim=3, **kw)
 
 
 @pytest.mark.gpu
