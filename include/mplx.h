@@ -232,6 +232,11 @@ int mplx_helper_touches(const mplx_ctx *ctx, uint32_t *touches);
  * lattices of at most 64 inputs, 0.5*w*dt for their larger lattices, 8*w*dt on the one-node kernels, 64*w*dt for LPA*.  A speed knob only: the
  * pop order -- and with it every result -- does not depend on it (tests/test_gpu_scale.py). */
 int mplx_set_bucket_width(mplx_ctx *ctx, double width);
+/* Slots of the state table per state of the node pool: 16 by default (load <= 1/16; env MPLX_TABLE_FACTOR sets the process's default), clamped
+ * to [1, 64] -- mplx_table_factor_clamp is that clamp.  Takes effect at the next allocation of the pools, which a changed factor forces at
+ * the next plan.  A speed and memory knob (and the tests' way to long probe paths): results do not depend on it. */
+int mplx_set_table_factor(mplx_ctx *ctx, int32_t slots_per_state);
+int32_t mplx_table_factor_clamp(int32_t slots_per_state);
 
 /* ---- env_map::get_succ for K nodes in one launch (unit-testable kernel entry).
  *      out: K x n_u records, record [k*n_u + i] belongs to control input i. ---- */

@@ -113,6 +113,8 @@ struct mplx_ctx {
   std::vector<uint32_t> chunk_bits_init;
   uint32_t chunk_word0[3] = {0, 0, 0}, chunk_words[3] = {0, 0, 0};
   bool last_recycled = false;
+  int32_t table_factor = 0;   // slots of the state table per pool state (mplx_set_table_factor); 0 = MPLX_TABLE_FACTOR, or 16
+  int32_t pool_table_factor = 0;  // what the table was allocated with
   bool pool_recycle = false;  // what the pools were allocated for (the table is sized for more states than the pool holds at once)
   unsigned long long *table_base = nullptr;  // the shared state table as allocated
   uint32_t tbl_epoch = TBL_EPOCHS;           // epoch of the table's slots of the last launch (table_prepare); TBL_EPOCHS: clear before use
@@ -743,6 +745,14 @@ extern "C" int mplx_set_pool_recycling(mplx_ctx *c, int32_t on) {
   c->recycle = on != 0;
   return MPLX_OK;
 }
+extern "C" int32_t mplx_table_factor_clamp(int32_t n) { return n < 1 ? 1 : n > 64 ? 64 : n; }
+extern "C" int mplx_set_table_factor(mplx_ctx *c, int32_t n) {
+  if (!c) return MPLX_ERR_ARG;
+  MPLX_REFUSE_PENDING(c);
+  c->cfg_epoch++;
+  c->table_factor = mplx_table_factor_clamp(n);  // (ensure_pools allocates anew when it differs from the table's)
+  return MPLX_OK;
+}
 extern "C" int mplx_set_bucket_width(mplx_ctx *c, double w) {
   if (!c || w < 0) return MPLX_ERR_ARG;
   c->cfg_epoch++;
@@ -979,7 +989,10 @@ static uint64_t next_pow2(uint64_t v) {
 
 static int ensure_pools(mplx_ctx *c, int slots) {
   const int control = c->cfg.control;
-  if (c->pools_valid && c->pool_slots >= slots && c->pool_control == control && c->pool_nodes == c->cap_nodes &&
+  // (measurement: slots per pool state.  Clamped: atoi of a negative value, taken as unsigned, sent next_pow2 round its loop for ever)
+  static const int32_t fac_env = getenv("MPLX_TABLE_FACTOR") ? mplx_table_factor_clamp((int32_t)atoi(getenv("MPLX_TABLE_FACTOR"))) : 0;
+  const int32_t fac = c->table_factor ? c->table_factor : fac_env ? fac_env : 16;
+  if (c->pools_valid && c->pool_slots >= slots && c->pool_table_factor == fac && c->pool_control == control && c->pool_nodes == c->cap_nodes &&
       c->pool_edges == c->cap_edges && c->pool_log == c->cap_log && (c->helpers != 0) == (c->pools.boxes != nullptr) && c->pool_recycle == c->recycle &&
       (c->helpers == 0 || c->pool_help_lanes == (c->cfg.n_u <= 31 ? 32 : 128)))
     return MPLX_OK;
@@ -1001,8 +1014,8 @@ static int ensure_pools(mplx_ctx *c, int slots) {
   // state (recycled pools of 256 M states: the table also keeps an entry for every state of the batch's finished queries), the
   // capped query alone 2011 vs 1974 ms with 4 vs 16.  Rounds 1-5 used 4.  The table is cleared once per 255 launches, not per batch
   // (table_prepare), so its size costs memory only: 32 GB at C4 size.
-  static const uint64_t fac_env = getenv("MPLX_TABLE_FACTOR") ? (uint64_t)atoi(getenv("MPLX_TABLE_FACTOR")) : 0;  // (measurement: slots per pool state)
-  const uint64_t T = std::min<uint64_t>(next_pow2((fac_env ? fac_env : 16ull) * (nch << NODE_CH_LOG)), 1ull << 32);
+  const uint64_t T = std::min<uint64_t>(next_pow2((uint64_t)fac * (nch << NODE_CH_LOG)), 1ull << 32);
+  c->pool_table_factor = fac;
   int r;
 #define PA(ptr, cnt) if ((r = pool_alloc(c, &(ptr), (cnt))) != MPLX_OK) { free_pools(c); return r; }
   PA(P.node_pool, (size_t)(nch << NODE_CH_LOG) * rec_bytes(control));

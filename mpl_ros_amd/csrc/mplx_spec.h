@@ -67,6 +67,10 @@
 #define MPLX_X_PROBE2 1       // (round 6) the look-up's first load brings the home slot AND its neighbour (almost always the same 64-byte line): a
                               // key whose home slot is taken by another state no longer costs the slowest lane of the batch a second dependent trip
 #endif
+#ifndef MPLX_X_LOOKUP_OVERLAP
+#define MPLX_X_LOOKUP_OVERLAP 1  // (HELP builds, units of 32 lanes) the look-up's first step settles from the two slot words the lane holds and asks for all it
+                                 // needs -- the claim of an empty slot OR the record an entry names -- before anything waits; 0: the parent's look-up (A/B)
+#endif
 #ifndef MPLX_X_HELP_TOUCH
 #define MPLX_X_HELP_TOUCH 1   // (HELP builds, units of 32 lanes) a helper loads the table slot and one word of the record of every successor it
                               // finds: the lines are on their way to the memory-side cache when the leader looks the successor up (helper_serve)
@@ -81,6 +85,20 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// The hot line of a state record -- 16 NW4 bytes from its start: g | h | flags pred key ... -- in 8-byte words, all requested back to back
+// and none of them movable: a relaxed workgroup-scope atomic load is a plain global_load_dwordx2 on gfx950 (see ld_u64_probe), and the
+// compiler neither sinks nor merges it.  Records are 8-byte aligned and at least 16 NW4 bytes long.
+template <int NW4>
+__device__ __forceinline__ void record_hot_line(const void *rec, uint32_t (&w)[4 * NW4]) {
+  const unsigned long long *r8 = (const unsigned long long *)rec;
+#pragma unroll
+  for (int j = 0; j < 2 * NW4; j++) {
+    const unsigned long long x = ld_u64_probe(&r8[j]);
+    w[2 * j] = (uint32_t)x;
+    w[2 * j + 1] = (uint32_t)(x >> 32);
+  }
 }
 
 // key_hash64 of candidate k's key (MPLX_X_KEY_HASH): written in 2a by the lane that checks the look-ahead record, read by the row
@@ -1436,21 +1454,48 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
             const uint32_t claim_batch = (batch_no & CLAIM_BATCH_MASK) << CLAIM_BATCH_SHIFT;
             static_assert(BLOCK <= (1 << CLAIM_BATCH_SHIFT), "the thread index of a claim has nine bits");
             const unsigned long long claim = tagq | (unsigned long long)(CLAIM_BASE + claim_batch + (uint32_t)tid);
-            // The claim of an empty slot goes out before the heuristic is computed, so that compare-and-swap's trip hides
-            // behind the f64 work.  The record a taken slot names does NOT: __builtin_prefetch emits no instruction on gfx950
-            // (a slot load, a prefetch of the record and the record load compile to two global_loads and nothing else), so the
-            // fetch of an existing state's record starts inside the probe loop, after the heuristic.  A real early load of one
-            // word of the record (consumed behind the record's own loads) was measured and not kept: bulk 127.0 against
-            // 125.6 ms, one more live register in a kernel that spills (profiles/key_hash_lds_speed.txt).  The call stays
-            // where it is: it costs nothing, and without it the compiler schedules every build of this kernel differently.
+            // First step of the look-up (MPLX_X_LOOKUP_OVERLAP; OVL builds: the flagship <32,16,ACC,help>).  Everything it needs is asked for before
+            // the wave waits, and consumed behind ONE wait.  From the slot words the lane already holds (v0, and v1 with MPLX_X_PROBE2):
+            //   * a home slot that is FINAL and not ours -- another tag, or this tag's TBL_DEAD_ID: neither changes within a launch epoch, rule
+            //     R3 -- is passed over at once, and the two cases below are decided on its neighbour (step0 = 1, vcur = v1);
+            //   * an empty slot is claimed here, ahead of the heuristic (compare-and-swap against the value seen): for an unhelped unit the trip
+            //     hides behind the f64 work, for a helped one (the helper's row: nothing to compute) behind the record loads of its neighbours;
+            //   * an entry with this query's tag has its record's hot line loaded BEHIND the heuristic, in a block of its own in front of the
+            //     probe loop, and compared there.  (Ahead of the heuristic, or carried into the loop's first iteration, the twelve words cost 19
+            //     spilled registers and 8 % of the flagship's step: profiles/lookup_overlap_speed.txt block 1.)
+            //   * a claim with this query's tag goes to the loop's slow path (re-read past the L1, bounded wait), unchanged.
+            // The probe order is the parent's: a slot is claimed only when every slot in front of it has been seen final-and-foreign or its record
+            // compared, so a lane whose home slot is an own-tag entry does NOT claim the neighbour early: it compares, then falls into the loop.
+            // The loop takes over at the position and with the value it would have had (pos, step0, vcur, first).
+            // The record loads are relaxed workgroup-scope atomic loads (plain global_loads on gfx950, like ld_u64_probe): the compiler moves no
+            // atomic load, whereas it sank the plain loads of g | h | flags | pred behind the key comparison -- a third dependent wait in a row
+            // (the parent's machine code: claim, key words, value words; profiles/lookup_overlap_speed.txt block 6 has both excerpts).
+            // Without OVL (helper-less builds, units of 128 lanes, the 27-input jerk build, MPLX_X_LOOKUP_OVERLAP=0) the look-up is the parent's,
+            // instruction for instruction: the claim alone goes out early; __builtin_prefetch emits no instruction on gfx950 and stays because
+            // every build of the kernel is scheduled differently without it.  A real early load of one record word was measured there and not
+            // kept (bulk 127.0 against 125.6 ms: profiles/key_hash_lds_speed.txt).  In the parent's flagship build the compiler put a
+            // s_waitcnt vmcnt(0) at the head of the f64 heuristic, right behind the claim (no register of the claim is touched there; what made
+            // the wait insertion place it was not found); this build's schedule has none.
             // (Computing the heuristic only for states found to be new, after the look-up, was measured slower: the slowest
             // lane of the workgroup sets the pace either way, and the overlap is lost.)
+            // (the 27-input jerk build, a hot line of 60 bytes, keeps the parent's look-up: with the peel it spills 127 registers against 49)
+            constexpr bool OVL = MPLX_X_LOOKUP_OVERLAP && HELP && UL == 32 && CONTROL == CTRL_ACC;
+            constexpr int NW4 = (24 + 4 * NKY + 15) / 16;
+            unsigned long long vcur = v0;
+            uint32_t step0 = 0;
+            if constexpr (OVL && MPLX_X_PROBE2) {
+              if (!MPLX_XF(P, 1) && !tbl_empty(v0, P.tbl_epoch) && ((v0 & 0xFFFFFFFF00000000ull) != tagq || (uint32_t)v0 == TBL_DEAD_ID)) {
+                pos = (pos0 + 1) & mask;
+                vcur = v1;
+                step0 = 1;
+              }
+            }
             unsigned long long cas0 = 0;
             bool did_cas0 = false;
-            if (tbl_empty(v0, P.tbl_epoch)) {  // (cleared, or left by a batch of another epoch: claimed against the value seen)
-              cas0 = atomicCAS(&P.table[pos], v0, claim);
+            if (tbl_empty(vcur, P.tbl_epoch)) {  // (cleared, or left by a batch of another epoch: claimed against the value seen)
+              cas0 = atomicCAS(&P.table[pos], vcur, claim);
               did_cas0 = true;
-            } else if ((uint32_t)v0 < CLAIM_BASE && (v0 & 0xFFFFFFFF00000000ull) == tagq) {
+            } else if (!OVL && (uint32_t)v0 < CLAIM_BASE && (v0 & 0xFFFFFFFF00000000ull) == tagq) {
               __builtin_prefetch(Q.node((uint32_t)v0), 0, 3);  // (no instruction on gfx950: see above)
             }
             MPLX_T2(S, 2, t2);
@@ -1486,8 +1531,32 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
 #ifdef MPLX_LOOKUP_TIMERS
             atomicMax(&S.arr_heur, (unsigned long long)__builtin_readcyclecounter());
 #endif
-            bool first = true;
-            for (uint32_t steps = 0;; steps++) {
+            bool first = true, settled = false;
+            if constexpr (OVL) {
+              // the first step of a lane whose slot names a state of this query, peeled: the record is asked for while the wave's
+              // compare-and-swaps are still out, and the one wait below brings both in
+              if (!did_cas0 && (uint32_t)vcur < CLAIM_BASE && (vcur & 0xFFFFFFFF00000000ull) == tagq) {
+                uint32_t w[4 * NW4];
+                record_hot_line<NW4>(Q.node((uint32_t)vcur), w);
+                uint32_t kd = 0;  // (the comparison of the loop's own record step, below)
+#pragma unroll
+                for (int i = 0; i < nk; i++) kd |= w[6 + i] ^ (uint32_t)L.key[i];
+                if constexpr (YAW) kd |= w[6 + nk] ^ (uint32_t)L.yaw_key;
+                if (kd == 0u) {
+                  S.bt_id[my_slot] = (uint32_t)vcur;
+                  S.bt_g[my_slot] = __hiloint2double((int)w[1], (int)w[0]);
+                  S.bt_h[my_slot] = __hiloint2double((int)w[3], (int)w[2]);
+                  S.bt_flags[my_slot] = w[4];
+                  S.bt_pred[my_slot] = w[5];
+                  settled = true;
+                } else {  // (another state of the query with the same tag byte: on, in the loop, from where it would have been)
+                  pos = (pos + 1) & mask;
+                  step0++;
+                  first = false;
+                }
+              }
+            }
+            if (!settled) for (uint32_t steps = step0;; steps++) {
               if (steps > (1u << 22)) {  // (a probe never walks this far in a table four times the node capacity)
                 S.status = 5;
                 guard_mark(P, GUARD_PROBE, (uint32_t)q, S.cyc[7], (unsigned long long)pos);
@@ -1496,9 +1565,9 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
 #if MPLX_X_PROBE2
               // (a view of the second slot as old as the first one's: rule R3 covers it the same way -- a stale EMPTY is caught by the
               //  compare-and-swap, an own-tag claim is read again past the L1, anything foreign moves the probe on)
-              unsigned long long v = first ? v0 : (steps == 1u && !MPLX_XF(P, 1)) ? v1 : MPLX_XF(P, 1) ? ld_u64(&P.table[pos]) : ld_u64_probe(&P.table[pos]);
+              unsigned long long v = first ? vcur : (steps == 1u && !MPLX_XF(P, 1)) ? v1 : MPLX_XF(P, 1) ? ld_u64(&P.table[pos]) : ld_u64_probe(&P.table[pos]);
 #else
-              unsigned long long v = first ? v0 : MPLX_XF(P, 1) ? ld_u64(&P.table[pos]) : ld_u64_probe(&P.table[pos]);
+              unsigned long long v = first ? vcur : MPLX_XF(P, 1) ? ld_u64(&P.table[pos]) : ld_u64_probe(&P.table[pos]);
 #endif
               if (tbl_empty(v, P.tbl_epoch)) {
                 unsigned long long old = (first && did_cas0) ? cas0 : atomicCAS(&P.table[pos], v, claim);
@@ -1538,14 +1607,18 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
               }
               const uint32_t vid = (uint32_t)v;
               if (vid < CLAIM_BASE && (v & 0xFFFFFFFF00000000ull) == tagq) {
-                // the record's hot line in 16-byte words, all asked for at once: g | h | flags pred key[0..1] | key[2..] ...
-                const uint4 *r4 = (const uint4 *)Q.node(vid);
-                constexpr int NW4 = (24 + 4 * NKY + 15) / 16;
                 uint32_t w[4 * NW4];
+                if constexpr (OVL) {
+                  record_hot_line<NW4>(Q.node(vid), w);
+                } else {
+                  // the record's hot line in 16-byte words.  (Asked for at once in the source only: the compiler sinks the loads of the
+                  // value words behind the key comparison -- see the note at the head of the look-up.)
+                  const uint4 *r4 = (const uint4 *)Q.node(vid);
 #pragma unroll
-                for (int j = 0; j < NW4; j++) {
-                  const uint4 x = r4[j];
-                  w[4 * j] = x.x; w[4 * j + 1] = x.y; w[4 * j + 2] = x.z; w[4 * j + 3] = x.w;
+                  for (int j = 0; j < NW4; j++) {
+                    const uint4 x = r4[j];
+                    w[4 * j] = x.x; w[4 * j + 1] = x.y; w[4 * j + 2] = x.z; w[4 * j + 3] = x.w;
+                  }
                 }
                 uint32_t kd = 0;
 #pragma unroll

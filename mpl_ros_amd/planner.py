@@ -599,6 +599,11 @@ class VoxelMapPlanner:
         ctx = self._ctx()
         ctx.check(ctx.lib.mplx_set_bucket_width(ctx.h, float(width)))
 
+    def setTableFactor(self, n):
+        """slots of the state table per pool state, clamped to [1, 64] (default 16); the pools are allocated anew at the next plan"""
+        ctx = self._ctx()
+        ctx.check(ctx.lib.mplx_set_table_factor(ctx.h, int(n)))
+
     def setSpeculation(self, mode):
         """-1 auto, 0 sequential kernel, 2 speculative multi-node expansion (same results)."""
         ctx = self._ctx()
