@@ -4,8 +4,11 @@
  * What MPL::PolyMapPlanner<3>::plan() (poly_map_planner.h of this shim) does on the device, with no reference header in
  * sight: the planner's set-up and its one world packed into the arrays of include/mplx.h's mplx_poly3_* calls, the plan
  * with the pool-doubling retry, and the read-back of the trajectory (actions, node ids, states), of the state space
- * (getCloseSet / getOpenSet) and of the expansion order (getExpandedNodes).  A program that does not have the reference's
- * headers -- a test driver -- plans through this header exactly as the shim's planner does.
+ * (getCloseSet / getOpenSet) and of the expansion order (getExpandedNodes).  The predecessor records behind
+ * getValidPrimitives / getAllPrimitives are fetched lazily (poly3_space_fetch: mplx_poly3_result_space / _edges / _blocked),
+ * keyed on mplx_poly3_plan_epoch by the rule of poly2_space.h: the device object serves every 3-D planner of the process, so
+ * when another planner has planned there since, the space is gone -- a red refusal, nothing fetched.  A program that does not
+ * have the reference's headers -- a test driver -- plans through this header exactly as the shim's planner does.
  */
 #ifndef MPLX_SHIM_POLY3_DEVICE_H
 #define MPLX_SHIM_POLY3_DEVICE_H
@@ -46,6 +49,17 @@ struct Poly3Plan {
   std::vector<int32_t> actions, node_ids, expanded;
   std::vector<double> states, node_pos;
   std::vector<int32_t> closed, opened;
+  uint64_t epoch = 0;  // mplx_poly3_plan_epoch of the shared device object right after this plan (0: no plan ran on the device)
+};
+/// the predecessor records of one 3-D plan on the host: states n x 13 (pos3 vel3 acc3 jrk3 t) in id order, the records with
+/// finite cost (child, parent, action) in push_back order and the blocked ones (parent, action), parents in id order
+struct Poly3Space {
+  bool fetched = false;          // states and valid records are here
+  bool blocked_fetched = false;  // the blocked records too
+  std::vector<double> states;
+  std::vector<int32_t> child, parent, action;
+  std::vector<int32_t> blocked_parent, blocked_action;
+  size_t n_nodes() const { return states.size() / 13; }
 };
 
 /// One device object serves every 3-D planner of the process (the reference constructs a new planner per plan: robot.hpp:109)
@@ -117,11 +131,54 @@ inline bool poly3_plan(const Poly3Query &q, Poly3Plan &out) {
     for (size_t i = 0; i < (size_t)n; i++)
       for (int k = 0; k < 3; k++) out.node_pos[3 * i + (size_t)k] = wps[i].pos[k];
   }
+  out.epoch = mplx_poly3_plan_epoch(p);  // (the lazy getters answer while this is still the device object's last plan)
   if (out.res.n_expanded > 0) {
     uint32_t ne = 0;
     out.expanded.resize((size_t)(out.res.n_expanded < rec ? out.res.n_expanded : rec));
     if (!poly3_check(p, mplx_poly3_result_expanded(p, 0, (uint32_t)out.expanded.size(), out.expanded.data(), &ne))) return false;
     out.expanded.resize(ne);
+  }
+  return true;
+}
+
+inline void poly3_refuse(const char *what, const char *why) { printf("\x1b[31m[PolyMapPlanner] %s refused: %s\n\x1b[0m", what, why); }
+/// Query 0 of the plan the caller noted `epoch` after (Poly3Plan::epoch).  with_blocked: the blocked records too (re-derived on
+/// the device when first asked for).  false: refused or a device call failed (the message is printed), `out` is left empty.
+/// A planner that has not planned on the device is refused without touching the device.
+inline bool poly3_space_fetch(uint64_t epoch, const mplx_result &res, bool with_blocked, Poly3Space &out, const char *what) {
+  if (epoch == 0) {
+    poly3_refuse(what, "this PolyMapPlanner3D has not planned on the device");
+    out = Poly3Space();
+    return false;
+  }
+  mplx_poly3 *p = poly3_shared_device();
+  if (!p || mplx_poly3_plan_epoch(p) != epoch) {
+    poly3_refuse(what, "another planner has planned on the shared device object since this planner's plan(): its state space is gone");
+    out = Poly3Space();
+    return false;
+  }
+  if (!out.fetched) {
+    out = Poly3Space();
+    const uint64_t n = res.n_nodes;
+    if (n > 0) {
+      out.states.resize((size_t)n * 13);
+      if (!poly3_check(p, mplx_poly3_result_space(p, 0, n, out.states.data(), nullptr, nullptr, nullptr, nullptr))) { out = Poly3Space(); return false; }
+      uint64_t ne = 0;
+      if (!poly3_check(p, mplx_poly3_result_edges(p, 0, 0, nullptr, nullptr, nullptr, &ne))) { out = Poly3Space(); return false; }
+      out.child.resize((size_t)ne); out.parent.resize((size_t)ne); out.action.resize((size_t)ne);
+      if (ne && !poly3_check(p, mplx_poly3_result_edges(p, 0, ne, out.child.data(), out.parent.data(), out.action.data(), &ne))) { out = Poly3Space(); return false; }
+    }
+    out.fetched = true;
+  }
+  if (with_blocked && !out.blocked_fetched) {
+    uint64_t nb = 0;
+    if (!poly3_check(p, mplx_poly3_result_blocked(p, 0, 0, nullptr, nullptr, &nb))) return false;
+    out.blocked_parent.resize((size_t)nb); out.blocked_action.resize((size_t)nb);
+    if (nb && !poly3_check(p, mplx_poly3_result_blocked(p, 0, nb, out.blocked_parent.data(), out.blocked_action.data(), &nb))) {
+      out.blocked_parent.clear(); out.blocked_action.clear();
+      return false;
+    }
+    out.blocked_fetched = true;
   }
   return true;
 }

@@ -16,7 +16,8 @@
  * an mplx_poly object and runs PlannerBase::plan there (time-keyed states, env_poly_map.h:63-64; cost
  * J + 0.001 J(VEL) + w dt, :71-73).  2-D like every in-tree caller (multi_robot_node.cpp, poly_map_planner_node.cpp); a
  * PolyMapPlanner3D (poly_map_planner.h:107, robot.hpp:229) plans through mplx_poly3_* instead, by way of the reference-free
- * plumbing of poly3_device.h, and serves getCloseSet / getOpenSet / getExpandedNodes from the device (3-D LPA* is refused).
+ * plumbing of poly3_device.h, and serves all five getters from the device too -- getValidPrimitives / getAllPrimitives lazily,
+ * through mplx_poly3_result_space / _edges / _blocked (3-D LPA* is refused).
  * A 2-D planner serves getCloseSet / getOpenSet / getExpandedNodes / getValidPrimitives / getAllPrimitives from the device as
  * well (poly_map_planner_node.cpp:105-124, poly_map_replanner_node.cpp:156-158,184,234), through the reference-free
  * poly2_space.h: lazily from the shared device object in A* mode, from its own LPA* handle with setLPAstar(true).
@@ -207,7 +208,8 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
     return ps;
   }
   /// Primitive(parent state, U[action], dt) of every predecessor record with finite cost / of every record, the blocked ones
-  /// included (poly_map_replanner_node.cpp:184,234).  3-D: refused, not served.
+  /// included (poly_map_replanner_node.cpp:184,234).  3-D: the same, from the records of the planner's last device plan (a planner
+  /// that has not planned on the device, or whose plan another planner has replaced since, is refused and returns nothing).
   vec_E<Primitive<Dim>> getValidPrimitives() const override { return primitives2(false, "getValidPrimitives()"); }
   vec_E<Primitive<Dim>> getAllPrimitives() const override { return primitives2(true, "getAllPrimitives()"); }
 
@@ -235,10 +237,7 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
   }
   vec_E<Primitive<Dim>> primitives2(bool all, const char *what) const {
     vec_E<Primitive<Dim>> prs;
-    if (Dim == 3) {
-      printf(ANSI_COLOR_RED "[PolyMapPlanner] %s refused: the mplx back-end serves the predecessor primitives of 2-D plans only (PolyMapPlanner3D: getCloseSet / getOpenSet / getExpandedNodes)\n" ANSI_COLOR_RESET, what);
-      return prs;
-    }
+    if (Dim == 3) return primitives3(all, what);
     if (!space2(all, what)) return prs;
     auto add = [&](int32_t parent, int32_t action) {
       if (parent < 0 || (size_t)parent >= space_.n_nodes() || action < 0 || (size_t)action >= this->U_vec_.size()) return;
@@ -251,6 +250,23 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
     for (size_t i = 0; i < space_.parent.size(); i++) add(space_.parent[i], space_.action[i]);
     if (all)
       for (size_t i = 0; i < space_.blocked_parent.size(); i++) add(space_.blocked_parent[i], space_.blocked_action[i]);
+    return prs;
+  }
+  /// the 3-D counterpart, in the same order: the finite records in push_back order, then -- when `all` -- the blocked ones
+  vec_E<Primitive<Dim>> primitives3(bool all, const char *what) const {
+    vec_E<Primitive<Dim>> prs;
+    if (!mplx_shim::poly3_space_fetch(plan3_.epoch, res_, all, space3_, what)) return prs;
+    auto add = [&](int32_t parent, int32_t action) {
+      if (parent < 0 || (size_t)parent >= space3_.n_nodes() || action < 0 || (size_t)action >= this->U_vec_.size()) return;
+      const double *st = &space3_.states[(size_t)parent * 13];
+      Waypoint<Dim> w((Control::Control)space_control_);
+      for (int k = 0; k < Dim && k < 3; k++) { w.pos(k) = st[k]; w.vel(k) = st[3 + k]; w.acc(k) = st[6 + k]; w.jrk(k) = st[9 + k]; }
+      w.t = st[12];
+      prs.push_back(Primitive<Dim>(w, this->U_vec_[(size_t)action], this->dt_));
+    };
+    for (size_t i = 0; i < space3_.parent.size(); i++) add(space3_.parent[i], space3_.action[i]);
+    if (all)
+      for (size_t i = 0; i < space3_.blocked_parent.size(); i++) add(space3_.blocked_parent[i], space3_.blocked_action[i]);
     return prs;
   }
   Vecf<Dim> pos3(size_t id) const {
@@ -277,6 +293,7 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
   /// state and action of every step, as the 2-D path builds it
   bool plan3(const Waypoint<Dim> &start, const Waypoint<Dim> &goal) {
     plan3_ = mplx_shim::Poly3Plan();
+    space3_ = mplx_shim::Poly3Space();
     if (this->use_lpastar_) {
       refuse3("plan() with setLPAstar(true)");
       return false;
@@ -443,6 +460,7 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
   uint64_t plan_epoch_ = 0;             // mplx_poly_plan_epoch of the shared device object right after this planner's A* plan (0: none)
   int32_t space_control_ = MPLX_ACC;
   mplx_shim::Poly3Plan plan3_;  // what the last 3-D plan left on the host (trajectory, state space, expansion order)
+  mutable mplx_shim::Poly3Space space3_;  // the predecessor records of the last 3-D plan, fetched by the first primitives getter that asks
 };
 
 typedef PolyMapPlanner<2> PolyMapPlanner2D;

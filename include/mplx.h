@@ -676,6 +676,9 @@ int mplx_poly3_plan_batch(mplx_poly3 *p, int32_t n, const int32_t *world_of, con
 int mplx_poly3_result_traj(mplx_poly3 *p, int32_t q, int32_t *actions, int32_t *node_ids, double *states);
 /* the state space of query q of the last batch (getCloseSet / getOpenSet): n_nodes states in id order, g, closed / opened flags */
 int mplx_poly3_result_nodes(mplx_poly3 *p, int32_t q, uint64_t cap, mplx_waypoint *states, double *g, int32_t *closed, int32_t *opened);
+/* the state-space export of a 3-D plan (mplx_poly3_result_space / _edges / _blocked / _space_ms, mplx_poly3_plan_epoch): declared in
+ * a header of its own, part of this one */
+#include "mplx_poly3_space.h"
 int mplx_poly3_set_record(mplx_poly3 *p, uint32_t cap_per_query);
 int mplx_poly3_result_expanded(mplx_poly3 *p, int32_t q, uint32_t cap, int32_t *ids, uint32_t *n);
 int mplx_poly3_set_deadline(mplx_poly3 *p, double seconds); /* launch guard of the search (mplx_set_deadline) */

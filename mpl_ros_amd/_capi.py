@@ -93,6 +93,10 @@ EXPORTS = [
     "mplx_poly3_set_capacity", "mplx_poly3_plan_batch", "mplx_poly3_result_traj", "mplx_poly3_result_nodes", "mplx_poly3_set_record",
     "mplx_poly3_result_expanded", "mplx_poly3_set_deadline", "mplx_poly3_last_kernel_ms",
 ]
+# what include/mplx_poly3_space.h declares (the header mplx.h includes for the state-space export of a 3-D plan)
+EXPORTS_POLY3_SPACE = [
+    "mplx_poly3_result_space", "mplx_poly3_result_edges", "mplx_poly3_result_blocked", "mplx_poly3_result_space_ms", "mplx_poly3_plan_epoch",
+]
 
 
 class PolySucc(C.Structure):
@@ -358,5 +362,11 @@ def load():
     L.mplx_poly3_result_expanded.argtypes = [P, C.c_int32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     L.mplx_poly3_set_deadline.argtypes = [P, C.c_double]
     L.mplx_poly3_last_kernel_ms.argtypes = [P, C.POINTER(C.c_float)]
+    L.mplx_poly3_result_space.argtypes = [P, C.c_int32, C.c_uint64] + [C.c_void_p] * 5
+    L.mplx_poly3_result_edges.argtypes = [P, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mplx_poly3_result_blocked.argtypes = [P, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mplx_poly3_result_space_ms.argtypes = [P, C.POINTER(C.c_float)]
+    L.mplx_poly3_plan_epoch.argtypes = [P]
+    L.mplx_poly3_plan_epoch.restype = C.c_uint64
     _lib = L
     return L

@@ -116,3 +116,21 @@ int mplx_ctx_ext_nodes(mplx_ctx *c, int q, uint64_t cap, mplx_waypoint *coords, 
   return MPLX_OK;
 }
 const char *mplx_ctx_ext_error(const mplx_ctx *c) { return c ? c->err.c_str() : ""; }
+
+// (mplx_ctx_ext_view) the last batch's pools, tables and outcomes for an export that runs in another translation unit
+int mplx_ctx_ext_view_get(const mplx_ctx *c, mplx_ctx_ext_view *out) {
+  if (!c || !out) return MPLX_ERR_ARG;
+  out->device = c->device;
+  out->stream = c->stream;
+  out->last_nq = c->last_nq;
+  out->pending = c->pending ? 1 : 0;
+  out->pools_valid = c->pools_valid ? 1 : 0;
+  out->recycled = c->last_recycled ? 1 : 0;
+  out->pool_control = c->pool_control;
+  out->last_out = c->last_out.data();
+  out->node_pool = c->pools.node_pool; out->edge_pool = c->pools.edge_pool;
+  out->node_chunks = c->pools.node_chunks; out->edge_chunks = c->pools.edge_chunks;
+  out->node_tables = c->d_node_tables; out->edge_tables = c->d_edge_tables;
+  out->plan_epoch = c->plan_epoch;
+  return MPLX_OK;
+}

@@ -12,6 +12,7 @@
 
 #include "mplx_ctx_ext.h"
 #include "mplx_poly3.h"
+#include "mplx_poly3_space.h"
 
 using namespace mplx;
 
@@ -42,6 +43,11 @@ struct mplx_poly3 {
   int world_cap = 0;
   mplx_ctx *ctx = nullptr;  // pools, batch buffers, guard and result getters of the search
   std::vector<int32_t> last_len;  // trajectory length of every query of the last plan_batch (0: no trajectory)
+  // the state-space export (mplx_poly3_space.hip): what the last plan ran with
+  uint64_t cfg_epoch = 0, commit_epoch = 0, plan_cfg_epoch = 0, plan_commit_epoch = 0;
+  bool plan_general = false;
+  std::vector<int32_t> plan_world_of;  // host copy: mplx_poly3_get_succ_batch re-uses d_world_of between the plan and the export
+  mplx_poly3_space *space = nullptr;
 };
 
 static int p3fail(mplx_poly3 *p, int code, const char *fmt, ...) {
@@ -87,6 +93,8 @@ extern "C" void mplx_poly3_destroy(mplx_poly3 *p) {
   (void)hipSetDevice(p->device);
   (void)hipStreamSynchronize(p->stream);
   poly3_free_dev(p);
+  mplx_poly3_space_free(p->space);
+  p->space = nullptr;
   (void)hipFree(p->d_U);
   (void)hipFree(p->d_world_of);
   mplx_ctx_destroy(p->ctx);
@@ -109,6 +117,7 @@ extern "C" int mplx_poly3_config(mplx_poly3 *p, int32_t control, int32_t n_u, co
   P3CHK(p, hipMemcpyAsync(p->d_U, p->U.data(), sizeof(double) * 3 * (size_t)n_u, hipMemcpyHostToDevice, p->stream));
   P3CHK(p, hipStreamSynchronize(p->stream));
   p->have_cfg = true;
+  p->cfg_epoch++;
   return MPLX_OK;
 }
 
@@ -212,6 +221,7 @@ extern "C" int mplx_poly3_commit(mplx_poly3 *p) {
   P3CHK(p, up(&p->d_worlds, p->worlds));
   P3CHK(p, hipStreamSynchronize(p->stream));
   p->committed = true;
+  p->commit_epoch++;
   return MPLX_OK;
 }
 // hyperplane equations above degree two can occur: JRK / SNP primitives, or an obstacle trajectory with such segments
@@ -342,6 +352,10 @@ extern "C" int mplx_poly3_plan_batch(mplx_poly3 *p, int32_t n, const int32_t *wo
   Poly3Launch L{poly3_dev(p), poly3_general(p)};
   p->last_len.clear();
   if (int r = from_ctx(p, mplx_ctx_ext_plan(p->ctx, n, in.data(), launch_search, &L, "the 3-D moving-obstacle search launch", out))) return r;
+  p->plan_cfg_epoch = p->cfg_epoch;
+  p->plan_commit_epoch = p->commit_epoch;
+  p->plan_general = L.general;
+  p->plan_world_of.assign(world_of, world_of + n);
   p->last_len.resize((size_t)n);
   for (int k = 0; k < n; k++) p->last_len[(size_t)k] = out[k].status == MPLX_PLAN_OK ? out[k].traj_len : 0;
   for (int k = 0; k < n; k++)
@@ -369,6 +383,25 @@ extern "C" int mplx_poly3_result_traj(mplx_poly3 *p, int32_t q, int32_t *actions
 extern "C" int mplx_poly3_result_nodes(mplx_poly3 *p, int32_t q, uint64_t cap, mplx_waypoint *coords, double *g, int32_t *closed, int32_t *opened) {
   if (!p) return MPLX_ERR_ARG;
   return from_ctx(p, mplx_ctx_ext_nodes(p->ctx, q, cap, coords, g, closed, opened));
+}
+// (internal: mplx_poly3_space.h) the view the state-space export works with
+int mplx_poly3_space_internal_view(mplx_poly3 *p, mplx_poly3_space_view *out) {
+  if (!p || !out) return MPLX_ERR_ARG;
+  out->dev = poly3_dev(p);
+  out->general = p->plan_general ? 1 : 0;
+  out->ctx = p->ctx;
+  out->plan_world_of = p->plan_world_of.data();
+  out->plan_n = (int32_t)p->plan_world_of.size();
+  out->commit_epoch = p->commit_epoch; out->plan_commit_epoch = p->plan_commit_epoch;
+  out->cfg_epoch = p->cfg_epoch; out->plan_cfg_epoch = p->plan_cfg_epoch;
+  out->space = &p->space;
+  return MPLX_OK;
+}
+int mplx_poly3_space_internal_fail(mplx_poly3 *p, int code, const char *msg) { return p3fail(p, code, "%s", msg); }
+// plan launches of the handle so far (a wrapper that shares the handle notices that somebody else planned on it since)
+extern "C" uint64_t mplx_poly3_plan_epoch(const mplx_poly3 *p) {
+  mplx_ctx_ext_view V;
+  return p && mplx_ctx_ext_view_get(p->ctx, &V) == MPLX_OK ? V.plan_epoch : 0;
 }
 extern "C" int mplx_poly3_set_record(mplx_poly3 *p, uint32_t cap) { return p ? from_ctx(p, mplx_set_record(p->ctx, cap)) : MPLX_ERR_ARG; }
 extern "C" int mplx_poly3_result_expanded(mplx_poly3 *p, int32_t q, uint32_t cap, int32_t *ids, uint32_t *n) {

@@ -5,10 +5,10 @@
 //
 // The search launch has completed (guard_wait + stream synchronisation in mplx_poly_plan_batch) before anything here runs, and the
 // kernels run on the context's stream: plain loads and stores, no cross-workgroup protocol, nothing of DESIGN 3.9.
-//   pass 1  poly_space_nodes_kernel : one lane per node id -> states[n][9], g, h, flag byte, length of the predecessor list
-//           poly_space_scan_kernel  : exclusive scan of the per-tile sums of those lengths (one workgroup), total
-//   pass 2  poly_space_edges_kernel : one lane per node walks its list again and writes (child, parent, action) at its offset, reversed
-//                                     (the device list is newest first, the reference's pred vectors grow by push_back)
+//   pass 1  space_nodes_kernel<Row2> : one lane per node id -> states[n][9], g, h, flag byte, length of the predecessor list
+//           space_scan_kernel        : exclusive scan of the per-tile sums of those lengths (one workgroup), total
+//   pass 2  space_edges_kernel       : one lane per node walks its list again and writes (child, parent, action) at its offset, reversed
+//   (mplx_space_passes.h: shared with the 3-D export, mplx_poly3_space.hip)
 //   pass 3  poly_space_blocked_kernel<GEN> : one 64-lane workgroup per closed node re-derives env_poly_map::get_succ (D7: the batched A*
 //                                     does not materialise blocked successors) -> one mask word per node, bit a = input a is blocked
 // One export per (plan epoch, q) is kept on the device: _nodes, _edges and _blocked of the same query do not repeat an earlier pass, and
@@ -21,150 +21,23 @@
 #include <vector>
 
 #include "mplx_poly_space.h"
+#include "mplx_space_passes.h"
 
 using namespace mplx;
 
 namespace {
 
-constexpr int TILE = 256;  // nodes per workgroup pass (divides a node chunk: the records of a tile are contiguous)
-static_assert(((1 << NODE_CH_LOG) % TILE) == 0, "a tile must not straddle a node chunk");
-constexpr uint32_t ERR_LIST = 1u, ERR_DEGREE = 2u, ERR_TABLE = 4u;
-
-struct SpaceArgs {
-  const char *node_pool, *edge_pool;
-  const uint32_t *node_table, *edge_table;  // of the query
-  uint32_t n_nodes, n_edges;
-  uint32_t node_chunks, edge_chunks;        // pool sizes: a table entry at or above them (NIL included) names no chunk
-  int32_t rb, hot, nk;                      // record bytes, hot-part bytes, state doubles
-  double *states, *g, *h;
-  uint8_t *flags;
-  uint32_t *len, *tile_sum;                 // per node / per tile (after the scan: exclusive prefix)
-  unsigned long long *total;
-  uint32_t *err;
-  int32_t *child, *parent, *action;
+// the exported row of a 2-D state: pos2 vel2 acc2 jrk2 t out of the pool's pos3 vel3 (acc3) t
+struct Row2 {
+  static constexpr int W = 9;
+  static __device__ __forceinline__ void decode(const double *st, int nk, double *o) {
+    o[0] = st[0]; o[1] = st[1];
+    o[2] = st[3]; o[3] = st[4];
+    o[4] = nk >= 9 ? st[6] : 0.0; o[5] = nk >= 9 ? st[7] : 0.0;
+    o[6] = 0.0; o[7] = 0.0;
+    o[8] = st[nk];
+  }
 };
-
-__device__ __forceinline__ const char *space_node(const SpaceArgs &A, uint32_t id) {
-  return A.node_pool + (((size_t)A.node_table[id >> NODE_CH_LOG] << NODE_CH_LOG) + (id & ((1u << NODE_CH_LOG) - 1u))) * (size_t)A.rb;
-}
-__device__ __forceinline__ const uint32_t *space_edge(const SpaceArgs &A, uint32_t e) {
-  return (const uint32_t *)(A.edge_pool + (((size_t)A.edge_table[e >> EDGE_CH_LOG] << EDGE_CH_LOG) + (e & ((1u << EDGE_CH_LOG) - 1u))) * (size_t)EDGE_BYTES);
-}
-
-// exclusive scan of v over the TILE lanes of the workgroup (LDS buffer sc[TILE]); total in `tot`
-__device__ __forceinline__ uint32_t tile_excl_scan(uint32_t v, uint32_t *sc, int tid, uint32_t &tot) {
-  sc[tid] = v;
-  __syncthreads();
-  for (int d = 1; d < TILE; d <<= 1) {
-    const uint32_t add = tid >= d ? sc[tid - d] : 0u;
-    __syncthreads();
-    sc[tid] += add;
-    __syncthreads();
-  }
-  const uint32_t incl = sc[tid];
-  tot = sc[TILE - 1];
-  __syncthreads();
-  return incl - v;
-}
-
-__global__ __launch_bounds__(TILE) void poly_space_nodes_kernel(SpaceArgs A) {
-  __shared__ double st_out[TILE * 9];  // the tile's states, written out in rows of consecutive doubles
-  __shared__ uint32_t sc[TILE];
-  const int tid = threadIdx.x;
-  const uint32_t n_tiles = (A.n_nodes + TILE - 1) / TILE;
-  for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const uint32_t id = tile * TILE + (uint32_t)tid;
-    uint32_t cnt = 0;
-    if (id < A.n_nodes) {
-      if (A.node_table[id >> NODE_CH_LOG] >= A.node_chunks) {
-        atomicOr(A.err, ERR_TABLE);
-        for (int d = 0; d < 9; d++) st_out[tid * 9 + d] = 0.0;
-      } else {
-        const char *r = space_node(A, id);
-        const double *hotp = (const double *)r;
-        const uint32_t *w = (const uint32_t *)(r + 16);
-        const uint32_t fl = w[0];
-        A.g[id] = hotp[0];
-        A.h[id] = hotp[1];
-        A.flags[id] = (uint8_t)(fl & (FLAG_CLOSED | FLAG_OPENED));
-        const double *st = (const double *)(r + A.hot);  // pos3 vel3 (acc3) t -- as mplx_ctx_ext_nodes decodes it
-        double *o = st_out + tid * 9;
-        o[0] = st[0]; o[1] = st[1];
-        o[2] = st[3]; o[3] = st[4];
-        o[4] = A.nk >= 9 ? st[6] : 0.0; o[5] = A.nk >= 9 ? st[7] : 0.0;
-        o[6] = 0.0; o[7] = 0.0;
-        o[8] = st[A.nk];
-        // length of the predecessor list: every index below n_edges, at most n_edges steps
-        for (uint32_t e = w[1]; e != NIL;) {
-          if (e >= A.n_edges || cnt >= A.n_edges || A.edge_table[e >> EDGE_CH_LOG] >= A.edge_chunks) {
-            atomicOr(A.err, ERR_LIST);
-            break;
-          }
-          cnt++;
-          e = space_edge(A, e)[1];
-        }
-        A.len[id] = cnt;
-      }
-    }
-    uint32_t tot;
-    (void)tile_excl_scan(cnt, sc, tid, tot);  // (its barriers also publish st_out)
-    if (tid == 0) A.tile_sum[tile] = tot;
-    const uint32_t first = tile * TILE, rows = A.n_nodes - first < (uint32_t)TILE ? A.n_nodes - first : (uint32_t)TILE;
-    for (uint32_t k = tid; k < rows * 9u; k += TILE) A.states[(size_t)first * 9 + k] = st_out[k];
-    __syncthreads();
-  }
-}
-
-// tile_sum[] -> exclusive prefix, in place; *total = sum.  One workgroup: 131072 tiles at the most (33 M states per query).
-__global__ __launch_bounds__(TILE) void poly_space_scan_kernel(SpaceArgs A) {
-  __shared__ uint32_t sc[TILE];
-  __shared__ unsigned long long carry;
-  const int tid = threadIdx.x;
-  const uint32_t n_tiles = (A.n_nodes + TILE - 1) / TILE;
-  if (tid == 0) carry = 0ull;
-  __syncthreads();
-  for (uint32_t base = 0; base < n_tiles; base += TILE) {
-    const uint32_t i = base + (uint32_t)tid;
-    const uint32_t v = i < n_tiles ? A.tile_sum[i] : 0u;
-    uint32_t tot;
-    const uint32_t ex = tile_excl_scan(v, sc, tid, tot);
-    const unsigned long long c = carry;
-    if (i < n_tiles) A.tile_sum[i] = (uint32_t)(c + ex);  // (the host compares *total with n_edges before an offset is used)
-    __syncthreads();
-    if (tid == 0) carry = c + tot;
-    __syncthreads();
-  }
-  if (tid == 0) *A.total = carry;
-}
-
-__global__ __launch_bounds__(TILE) void poly_space_edges_kernel(SpaceArgs A) {
-  __shared__ uint32_t sc[TILE];
-  const int tid = threadIdx.x;
-  const uint32_t n_tiles = (A.n_nodes + TILE - 1) / TILE;
-  for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const uint32_t id = tile * TILE + (uint32_t)tid;
-    const uint32_t cnt = id < A.n_nodes ? A.len[id] : 0u;
-    uint32_t tot;
-    const uint32_t off = A.tile_sum[tile] + tile_excl_scan(cnt, sc, tid, tot);
-    if (cnt) {
-      const uint32_t *w = (const uint32_t *)(space_node(A, id) + 16);
-      uint32_t k = 0;
-      for (uint32_t e = w[1]; e != NIL && k < cnt; k++) {
-        if (e >= A.n_edges) { atomicOr(A.err, ERR_LIST); break; }
-        const uint32_t *er = space_edge(A, e);  // {parent, next, action}
-        const size_t at = (size_t)off + (cnt - 1u - k);
-        if (at < (size_t)A.n_edges) {
-          A.child[at] = (int32_t)id;
-          A.parent[at] = (int32_t)er[0];
-          A.action[at] = (int32_t)(er[2] & EDGE_ACTION_MASK);
-        } else {
-          atomicOr(A.err, ERR_LIST);
-        }
-        e = er[1];
-      }
-    }
-  }
-}
 
 // env_poly_map::get_succ of the closed states of query q, as poly_get_succ_kernel (mplx_poly_search.h) runs it -- the state comes from
 // the pool record, the world is world_of[q], t_rel = t - W.start_t -- with one word per node as the outcome: bit a is set iff primitive a
@@ -208,22 +81,6 @@ __global__ __launch_bounds__(64) void poly_space_blocked_kernel(PolyDev D, Space
     __syncthreads();
   }
 }
-
-template <typename T>
-struct Buf {  // a device buffer that grows on demand
-  T *d = nullptr;
-  size_t cap = 0;
-  hipError_t need(size_t n) {
-    if (n <= cap) return hipSuccess;
-    (void)hipFree(d);
-    d = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void **)&d, sizeof(T) * n);
-    if (e == hipSuccess) cap = n;
-    return e;
-  }
-  void release() { (void)hipFree(d); d = nullptr; cap = 0; }
-};
 
 }  // namespace
 
@@ -302,7 +159,6 @@ SpaceArgs space_args(const mplx_poly_space_view &V, const mplx_poly_space &S, in
   A.child = S.child.d; A.parent = S.parent.d; A.action = S.action.d;
   return A;
 }
-int grid_for(size_t items) { return (int)(items < 4096 ? (items ? items : 1) : 4096); }
 
 int space_err(mplx_poly *p, mplx_poly_space &S, uint32_t err) {
   S.q = -1;  // nothing of this export is kept
@@ -325,8 +181,8 @@ int space_nodes(mplx_poly *p, const mplx_poly_space_view &V, int32_t q, const Qu
   if (!S->ev0) { SCHK(p, hipEventCreate(&S->ev0)); SCHK(p, hipEventCreate(&S->ev1)); }
   SCHK(p, hipMemsetAsync(S->total.d, 0, 2 * sizeof(unsigned long long), V.stream));
   SCHK(p, hipEventRecord(S->ev0, V.stream));
-  hipLaunchKernelGGL(poly_space_nodes_kernel, dim3(grid_for(n_tiles)), dim3(TILE), 0, V.stream, A);
-  hipLaunchKernelGGL(poly_space_scan_kernel, dim3(1), dim3(TILE), 0, V.stream, A);
+  hipLaunchKernelGGL(space_nodes_kernel<Row2>, dim3(grid_for(n_tiles)), dim3(TILE), 0, V.stream, A);
+  hipLaunchKernelGGL(space_scan_kernel, dim3(1), dim3(TILE), 0, V.stream, A);
   SCHK(p, hipGetLastError());
   SCHK(p, hipEventRecord(S->ev1, V.stream));
   unsigned long long back[2] = {0, 0};
@@ -392,7 +248,7 @@ extern "C" int mplx_poly_result_edges(mplx_poly *p, int32_t q, uint64_t cap, int
     SCHK(p, S->child.need(ne)); SCHK(p, S->parent.need(ne)); SCHK(p, S->action.need(ne));
     const SpaceArgs A = space_args(V, *S, q, *o);
     SCHK(p, hipEventRecord(S->ev0, V.stream));
-    hipLaunchKernelGGL(poly_space_edges_kernel, dim3(grid_for(((size_t)o->n_nodes + TILE - 1) / TILE)), dim3(TILE), 0, V.stream, A);
+    hipLaunchKernelGGL(space_edges_kernel, dim3(grid_for(((size_t)o->n_nodes + TILE - 1) / TILE)), dim3(TILE), 0, V.stream, A);
     SCHK(p, hipGetLastError());
     SCHK(p, hipEventRecord(S->ev1, V.stream));
     unsigned long long back[2] = {0, 0};

@@ -176,6 +176,62 @@ class PolyTeam3D:
             st[i, 0:3], st[i, 3:6], st[i, 6:9], st[i, 9:12], st[i, 12] = wps[i].pos[:], wps[i].vel[:], wps[i].acc[:], wps[i].jrk[:], wps[i].t
         return st, g[:n], closed[:n], opened[:n]
 
+    def plan_epoch(self):
+        """plan launches of the handle so far"""
+        return int(self.lib.mplx_poly3_plan_epoch(self.h))
+
+    def state_space(self, q):
+        """The state space of query q of the last plan_batch, exported on the device (mplx_poly3_result_space / _edges): states n x 13
+        (pos3 vel3 acc3 jrk3 t) in id order, g, h, closed / opened flags, and the predecessor records (child, parent, action), children
+        in id order, each child's records oldest first.  The names are those of PolyTeam.state_space()."""
+        q = int(q)
+        n = int(self._results[q].n_nodes)
+        states = np.zeros((max(n, 1), 13)); g = np.zeros(max(n, 1)); h = np.zeros(max(n, 1))
+        closed = np.zeros(max(n, 1), dtype=np.int32); opened = closed.copy()
+        self.check(self.lib.mplx_poly3_result_space(self.h, q, n, states.ctypes.data, g.ctypes.data, h.ctypes.data, closed.ctypes.data, opened.ctypes.data))
+        ne = C.c_uint64()
+        self.check(self.lib.mplx_poly3_result_edges(self.h, q, 0, None, None, None, C.byref(ne)))
+        m = int(ne.value)
+        child = np.zeros(max(m, 1), dtype=np.int32); parent = child.copy(); action = child.copy()
+        if m:
+            self.check(self.lib.mplx_poly3_result_edges(self.h, q, m, child.ctypes.data, parent.ctypes.data, action.ctypes.data, C.byref(ne)))
+        return dict(n_nodes=n, states=states[:n], g=g[:n], h=h[:n], closed=closed[:n], opened=opened[:n],
+                    child=child[:m], parent=parent[:m], action=action[:m])
+
+    def blocked(self, q):
+        """(parent, action) of the successors with cost +inf of the states closed at the end of query q's search, parents in id order,
+        actions ascending (mplx_poly3_result_blocked: re-derived on the device; refused once the worlds or the set-up have changed)."""
+        q = int(q)
+        nb = C.c_uint64()
+        self.check(self.lib.mplx_poly3_result_blocked(self.h, q, 0, None, None, C.byref(nb)))
+        m = int(nb.value)
+        parent = np.zeros(max(m, 1), dtype=np.int32); action = parent.copy()
+        if m:
+            self.check(self.lib.mplx_poly3_result_blocked(self.h, q, m, parent.ctypes.data, action.ctypes.data, C.byref(nb)))
+        return parent[:m], action[:m]
+
+    def space_ms(self):
+        """(measurement) kernel ms of the last first pass (nodes + scan), edges pass and blocked pass of the state-space export"""
+        ms = (C.c_float * 3)()
+        self.check(self.lib.mplx_poly3_result_space_ms(self.h, ms))
+        return [float(x) for x in ms]
+
+    def _flag_positions(self, q, want_closed):
+        q = int(q)
+        n = int(self._results[q].n_nodes)
+        states = np.zeros((max(n, 1), 13)); closed = np.zeros(max(n, 1), dtype=np.int32); opened = closed.copy()
+        self.check(self.lib.mplx_poly3_result_space(self.h, q, n, states.ctypes.data, None, None, closed.ctypes.data, opened.ctypes.data))
+        sel = closed[:n] != 0 if want_closed else (opened[:n] != 0) & (closed[:n] == 0)
+        return states[:n][sel][:, 0:3].copy()
+
+    def close_set(self, q):
+        """getCloseSet(): positions of the states with the closed flag, in id order"""
+        return self._flag_positions(q, True)
+
+    def open_set(self, q):
+        """getOpenSet(): positions of the states that are opened and not closed, in id order"""
+        return self._flag_positions(q, False)
+
     def expanded_ids(self, q):
         cap = int(self._results[q].n_expanded)
         ids = np.zeros(max(cap, 1), dtype=np.int32)
