@@ -71,6 +71,17 @@
 #define MPLX_X_LOOKUP_OVERLAP 1  // (HELP builds, units of 32 lanes) the look-up's first step settles from the two slot words the lane holds and asks for all it
                                  // needs -- the claim of an empty slot OR the record an entry names -- before anything waits; 0: the parent's look-up (A/B)
 #endif
+#ifndef MPLX_X_ROW_TRAVEL
+#define MPLX_X_ROW_TRAVEL 1   // (HELP builds, units of 32 lanes) the last word of a look-ahead row -- voxel reads | check word -- stays a whole 64-bit value from its
+                              // request in 2a to its uses: narrowed AT the request it made the wave wait for the row on the spot, ahead of the expansion
+#endif
+// Measured with it and NOT kept (profiles/row_travel_speed.txt; every variant returned identical results): the leader's posted stores taken out
+// of its waits --
+//   * wish list and seq stored behind the row request instead of in front of the first use of the prefetched records (whose wait, in wave 0,
+//     also collects the stores' write-through acknowledgements: 700-900 cycles per batch on that wave's clock): the wait goes, the look-ahead
+//     hits fall (the list reaches the helpers ~4 k cycles later) and the long query alone runs 1 % slower;
+//   * box->n_expanded stored at the head of the batch instead of in front of its last barrier: no change alone, the blocking step +1 %;
+//   * box->helpers asked for at the head of the batch and taken in 2a: no change (two batches of eight, behind thread 0's counters anyway).
 #ifndef MPLX_X_HELP_TOUCH
 #define MPLX_X_HELP_TOUCH 1   // (HELP builds, units of 32 lanes) a helper loads the table slot and one word of the record of every successor it
                               // finds: the lines are on their way to the memory-side cache when the leader looks the successor up (helper_serve)
@@ -166,7 +177,7 @@ struct SmemSpec : Smem<UL * K, K, NCAP_> {
   [[no_unique_address]] KeyHashLds<NHASH> kh;  // (behind the product build's other words, which keep their offsets)
 #ifdef MPLX_LOOKUP_TIMERS
   unsigned long long cyc2[24];
-  unsigned long long cycw[16][4];
+  unsigned long long cycw[16][6];  // per wave: [0..3] expansion and the look-up's sections, [4] candidates' records arrive, [5] goal test .. row request (2a)
   unsigned long long arr_max, arr_heur, sum_heur, sum_arr;
   unsigned long long dbg_n, dbg_na, dbg_slow, dbg_n256, dbg_pulls;
 #endif
@@ -763,7 +774,7 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
       S.n_sorted = 0;
 #ifdef MPLX_LOOKUP_TIMERS
       for (int i = 0; i < 24; i++) S.cyc2[i] = 0;
-      for (int i = 0; i < 64; i++) (&S.cycw[0][0])[i] = 0;
+      for (int i = 0; i < 96; i++) (&S.cycw[0][0])[i] = 0;
       S.arr_max = 0; S.arr_heur = 0; S.sum_heur = 0; S.sum_arr = 0;
       S.dbg_n = S.dbg_na = S.dbg_slow = S.dbg_n256 = S.dbg_pulls = 0;
 #endif
@@ -888,6 +899,9 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
         }
         MPLX_TIC(tp);
         [[maybe_unused]] unsigned long long t3 = __builtin_readcyclecounter();
+#ifdef MPLX_LOOKUP_TIMERS
+        unsigned long long t2a = 0;
+#endif
         batch_no++;
         if (S.n_near == 0) {
           __syncthreads();
@@ -1144,6 +1158,9 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
           }
           lds_barrier();
           MPLX_T2(S, 19, t3);
+#ifdef MPLX_LOOKUP_TIMERS
+          t2a = __builtin_readcyclecounter();  // (2a per wave, S.cycw[..][4..5]: thread 0's clock alone cannot tell wave 0's store acknowledgements from a record's arrival)
+#endif
           if constexpr (HELP) {
             // wish list: the front of what is left of OPEN (sorted) = the candidates of the next batches.  Announced
             // by the seq store right behind it (MPLX_X_WISH_NOW; the same wave, no wait in between): its first sixteen
@@ -1151,6 +1168,9 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
             // reached the helpers when those entries were being selected -- every state that pops two batches after its
             // creation missed its look-ahead record by construction.  A helper that sees the seq ahead of some of the list's
             // words reads the list of two batches ago in their place: records of this query, most of them served (performance only).
+            // (These stores stand between the prefetched records' loads and their first use: in wave 0 that use's wait -- the counter runs in order --
+            //  also collects their write-through acknowledgements, 700-900 cycles of S.cycw[0][4] over the other waves'.  Issued behind the row
+            //  request instead, the list is late for the helpers: measured, and lost -- see MPLX_X_ROW_TRAVEL above.)
             if (S.helped && tid < WISH) {
               unsigned long long v = ~0ull;
               if ((uint32_t)tid < n - kc) v = ((unsigned long long)((uint32_t)q & 0xFFFFu) << 48) | (unsigned long long)Q.node_rec(S.near_id[tid]);
@@ -1218,6 +1238,9 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
         }
         unit_sync<UL>();
         MPLX_T2(S, 20, t3);
+#ifdef MPLX_LOOKUP_TIMERS
+        if ((tid & 63) == 0) { const unsigned long long now_ = __builtin_readcyclecounter(); S.cycw[tid >> 6][4] += now_ - t2a; t2a = now_; }
+#endif
         if constexpr (FILTER) {  // the candidate's key in the filter table: expandable?
           if (live_unit && lu == 0) {
             const FilterView F = filter_view(P);
@@ -1278,11 +1301,18 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
         }
         unit_sync<UL>();
         // the helper's row of a cached candidate -- the heuristics of its successors, the voxel-read count -- is asked
-        // for now (agent-scope loads: always a trip to memory) so that it travels during the expansion; used in 2b / 2c
+        // for now (agent-scope loads: always a trip to memory) so that it travels during the expansion; used in 2b / 2c.
+        // In the machine code of a hit unit (profiles/row_travel_isa.txt) the first s_waitcnt vmcnt that covers these loads stands in front of
+        // the S.u_reads store behind the unit scans; the waits in between (node cell, sampling loop) belong to branches a hit unit does not enter.
         [[maybe_unused]] double h_row = 0.0;
         [[maybe_unused]] unsigned long long reads_word = 0ull;  // (units of 32 lanes: voxel reads | check word of the row << 32)
         [[maybe_unused]] unsigned long long h_tag = 0ull, reads_tag = 0ull;  // (MPLX_X_ROW_PAIRS: the checks of this lane's heuristic and of the reads)
-        [[maybe_unused]] uint32_t reads_row = 0u;  // (32 bits asked for: a 64-bit load whose upper half is dead makes the compiler wait for it at once, to reuse the register)
+        // (units of 128 lanes ask for the 32 bits they use: a 64-bit load whose upper half is dead makes the compiler wait for it at once, to
+        //  reuse the register.  Units of 32 lanes need both halves -- and a (uint32_t)reads_word taken AT the request did the same: a v_mov behind
+        //  the load, with an s_waitcnt vmcnt(0) in front of it that exposed the whole trip, h_row's included, ahead of the expansion.
+        //  MPLX_X_ROW_TRAVEL: the word stays whole and is narrowed at its uses, behind the unit scans and behind the row check.)
+        [[maybe_unused]] uint32_t reads_row = 0u;
+        [[maybe_unused]] constexpr bool ROW_WHOLE = MPLX_X_ROW_TRAVEL && HELP && UL == 32;
 #if MPLX_X_EARLY_ROW
         if constexpr (HELP) {
           const uint32_t rp1 = live_unit ? S.hc_row[ku] : 0u;
@@ -1301,7 +1331,7 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
             if (lu == 0) {
               if constexpr (UL == 32) {
                 reads_word = ld_u64((const unsigned long long *)&row[cache_reads_slot(UL)]);
-                reads_row = (uint32_t)reads_word;
+                if (!MPLX_X_ROW_TRAVEL) reads_row = (uint32_t)reads_word;
               } else {
                 reads_row = ld_u32((const uint32_t *)&row[cache_reads_slot(UL)]);
               }
@@ -1310,6 +1340,9 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
         }
 #endif
         MPLX_T2(S, 21, t3);
+#ifdef MPLX_LOOKUP_TIMERS
+        if ((tid & 63) == 0) S.cycw[tid >> 6][5] += __builtin_readcyclecounter() - t2a;
+#endif
         MPLX_TOC(S, 0, tp);
         // ---- 2b. expand all live units concurrently
         MPLX_TIC(tx);
@@ -1339,7 +1372,7 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
             S.u_fin[ku] = tot >> 10;
             if (HELP && S.hc_row[ku] != 0u)  // voxel reads of the expansion as the helper counted them (slot 31 of its row)
 #if MPLX_X_EARLY_ROW
-              S.u_reads[ku] = reads_row;  // (units of 32 lanes: written again once the row has passed its check, before the barrier of 2c)
+              S.u_reads[ku] = ROW_WHOLE ? (uint32_t)reads_word : reads_row;  // (units of 32 lanes: written again once the row has passed its check, before the barrier of 2c)
 #else
               S.u_reads[ku] = (uint32_t)ld_u64((const unsigned long long *)&P.cache_h[(size_t)(S.hc_row[ku] - 1u) * cache_row_doubles(UL) + cache_reads_slot(UL)]);
 #endif
@@ -1419,10 +1452,10 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
               if (want) h_row = ld_f64_agent(&row[cache_h_slot(UL, lu)]);
               if (lu == 0) {
                 reads_word = ld_u64((const unsigned long long *)&row[cache_reads_slot(UL)]);
-                reads_row = (uint32_t)reads_word;
+                if (!MPLX_X_ROW_TRAVEL) reads_row = (uint32_t)reads_word;
               }
             }
-            if (lu == 0) S.u_reads[ku] = reads_row;
+            if (lu == 0) S.u_reads[ku] = MPLX_X_ROW_TRAVEL ? (uint32_t)reads_word : reads_row;
           }
         }
 #endif
@@ -1936,7 +1969,7 @@ __global__ __launch_bounds__(UL *K) void astar_spec_kernel(SearchParams P) {
       for (int i = 0; i < 24; i++) printf(" %llu", S.cyc2[i] / (S.cyc[7] ? S.cyc[7] : 1ull));
       printf("\n  max-over-lanes: heuristic done %llu, barrier arrival %llu\n", S.sum_heur / S.cyc[7], S.sum_arr / S.cyc[7]);
       printf("  ranking: mean near size %.1f, mean appended %.1f, batches on the all-pairs path %llu, batches with near > 256: %llu, of %llu\n", (double)S.dbg_n / S.cyc[7], (double)S.dbg_na / S.cyc[7], S.dbg_slow, S.dbg_n256, S.cyc[7]);
-      for (int j = 0; j < 4; j++) { printf("  per-wave %d:", j); for (int w = 0; w < BLOCK / 64; w++) printf(" %llu", S.cycw[w][j] / (S.cyc[7] ? S.cyc[7] : 1ull)); printf("\n"); }
+      for (int j = 0; j < 6; j++) { printf("  per-wave %d:", j); for (int w = 0; w < BLOCK / 64; w++) printf(" %llu", S.cycw[w][j] / (S.cyc[7] ? S.cyc[7] : 1ull)); printf("\n"); }
       }
 #endif
     }
