@@ -684,6 +684,41 @@ int mplx_poly3_result_expanded(mplx_poly3 *p, int32_t q, uint32_t cap, int32_t *
 int mplx_poly3_set_deadline(mplx_poly3 *p, double seconds); /* launch guard of the search (mplx_set_deadline) */
 int mplx_poly3_last_kernel_ms(const mplx_poly3 *p, float *ms);
 
+/* ---- LPA* of the 3-D moving-obstacle planner: PolyMapPlanner3D with setLPAstar(true), updateNodes(), getSubStateSpace().
+ *      mplx_plpa_* one for one, on an mplx_poly3 handle (its lattice, limits and committed worlds); states are 13 doubles
+ *      (pos3 vel3 acc3 jrk3 t).  One state space per handle, in pools private to it: an mplx_poly3_plan_batch on the same mplx_poly3
+ *      between two calls leaves it untouched; mplx_poly3_config after it was built drops it.  Refused with MPLX_ERR_ARG before any
+ *      launch: an mplx_poly3 that is not configured or not committed, VEL or SNP control, a world index out of range.  The launch
+ *      honours mplx_poly3_set_deadline (MPLX_ERR_TIMEOUT; the space is dropped).  Destroy it before the mplx_poly3. ---- */
+typedef struct mplx_plpa3 mplx_plpa3;
+int mplx_plpa3_create(mplx_poly3 *p, mplx_plpa3 **out);  /* no device work; p NULL (a failed mplx_poly3_create): MPLX_ERR_ARG */
+void mplx_plpa3_destroy(mplx_plpa3 *l);
+const char *mplx_plpa3_last_error(const mplx_plpa3 *l);  /* l may be NULL: last create error */
+int mplx_plpa3_set_capacity(mplx_plpa3 *l, uint64_t max_nodes, uint64_t max_edges, uint64_t max_open_log);  /* 0 = keep; drops the space */
+int mplx_plpa3_initialized(const mplx_plpa3 *l);  /* PlannerBase::initialized() */
+int mplx_plpa3_reset(mplx_plpa3 *l);              /* drop the state space */
+/* PlannerBase::plan: the space of the last plan is repaired when it is valid, the goal is the same and the start is its root;
+ * otherwise (and after another eps / tolerance / heuristic mode) a new one is started.  A capped plan (MPLX_PLAN_MAX_EXPAND)
+ * leaves a space the next call goes on repairing.  start / goal: 13 doubles. */
+int mplx_plpa3_plan(mplx_plpa3 *l, int32_t world, const double *start, const double *goal, double eps, double tol_pos, double tol_vel, int32_t max_expand,
+                    int32_t heur_ignore_dynamics, mplx_result *out);
+/* PolyMapPlanner::updateNodes after the world was committed again: every predecessor entry re-tested; n_blocked / n_cleared: entries
+ * that became blocked / free; mplx_plpa3_changed lists them by entry number. */
+int mplx_plpa3_update_nodes(mplx_plpa3 *l, int32_t world, uint64_t *n_blocked, uint64_t *n_cleared);
+int mplx_plpa3_changed(mplx_plpa3 *l, uint64_t cap, int32_t *entry, int32_t *now_blocked, uint64_t *n);
+/* getSubStateSpace(time_step): by planning afresh from the time_step-th state of the last trajectory; the stored trajectory is dropped */
+int mplx_plpa3_sub_state_space(mplx_plpa3 *l, int32_t world, int32_t time_step);
+int mplx_plpa3_traj_len(const mplx_plpa3 *l);
+/* trajectory of the last successful plan, start -> goal: actions[len], node_ids[len + 1], states (len + 1) x 13; NULLs allowed */
+int mplx_plpa3_result_traj(mplx_plpa3 *l, int32_t *actions, int32_t *node_ids, double *states);
+int mplx_plpa3_last_kernel_ms(const mplx_plpa3 *l, float *ms);
+int mplx_plpa3_counts(const mplx_plpa3 *l, uint64_t *n_nodes, uint64_t *n_entries);
+int mplx_plpa3_result_expanded(mplx_plpa3 *l, uint32_t cap, int32_t *ids, uint32_t *n);
+/* state-space dump, arrays of `cap` states: states x 13 | g rhs h | closed opened built */
+int mplx_plpa3_result_nodes(mplx_plpa3 *l, uint64_t cap, double *states, double *g, double *rhs, double *h, int32_t *closed, int32_t *opened, int32_t *built);
+/* predecessor entries in creation order, arrays of `cap` entries: child, parent, action, blocked */
+int mplx_plpa3_result_entries(mplx_plpa3 *l, uint64_t cap, int32_t *child, int32_t *parent, int32_t *action, int32_t *blocked);
+
 /* ---- after the search: refinement and sampling (host arithmetic, no context, no device) ----
  * TrajSolver3D(control).setWaypoints(wps).setDts(dts).solve(), map_planner_node.cpp:217-227: minimum-derivative
  * piecewise polynomial through n_wp waypoints (control kind VEL / ACC / JRK: minimum velocity / acceleration / jerk);

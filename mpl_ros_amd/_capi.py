@@ -92,6 +92,9 @@ EXPORTS = [
     "mplx_poly3_add_static", "mplx_poly3_add_linear", "mplx_poly3_add_nonlinear", "mplx_poly3_commit", "mplx_poly3_get_succ_batch",
     "mplx_poly3_set_capacity", "mplx_poly3_plan_batch", "mplx_poly3_result_traj", "mplx_poly3_result_nodes", "mplx_poly3_set_record",
     "mplx_poly3_result_expanded", "mplx_poly3_set_deadline", "mplx_poly3_last_kernel_ms",
+    "mplx_plpa3_create", "mplx_plpa3_destroy", "mplx_plpa3_last_error", "mplx_plpa3_set_capacity", "mplx_plpa3_initialized", "mplx_plpa3_reset",
+    "mplx_plpa3_plan", "mplx_plpa3_update_nodes", "mplx_plpa3_changed", "mplx_plpa3_sub_state_space", "mplx_plpa3_traj_len", "mplx_plpa3_result_traj",
+    "mplx_plpa3_last_kernel_ms", "mplx_plpa3_counts", "mplx_plpa3_result_expanded", "mplx_plpa3_result_nodes", "mplx_plpa3_result_entries",
 ]
 # what include/mplx_poly3_space.h declares (the header mplx.h includes for the state-space export of a 3-D plan)
 EXPORTS_POLY3_SPACE = [
@@ -368,5 +371,24 @@ def load():
     L.mplx_poly3_result_space_ms.argtypes = [P, C.POINTER(C.c_float)]
     L.mplx_poly3_plan_epoch.argtypes = [P]
     L.mplx_poly3_plan_epoch.restype = C.c_uint64
+    L.mplx_plpa3_create.argtypes = [P, C.POINTER(P)]
+    L.mplx_plpa3_destroy.argtypes = [P]
+    L.mplx_plpa3_destroy.restype = None
+    L.mplx_plpa3_last_error.argtypes = [P]
+    L.mplx_plpa3_last_error.restype = C.c_char_p
+    L.mplx_plpa3_set_capacity.argtypes = [P, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.mplx_plpa3_initialized.argtypes = [P]
+    L.mplx_plpa3_reset.argtypes = [P]
+    L.mplx_plpa3_plan.argtypes = [P, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.POINTER(Result)]
+    L.mplx_plpa3_update_nodes.argtypes = [P, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.mplx_plpa3_changed.argtypes = [P, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.mplx_plpa3_sub_state_space.argtypes = [P, C.c_int32, C.c_int32]
+    L.mplx_plpa3_traj_len.argtypes = [P]
+    L.mplx_plpa3_result_traj.argtypes = [P, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mplx_plpa3_last_kernel_ms.argtypes = [P, C.POINTER(C.c_float)]
+    L.mplx_plpa3_counts.argtypes = [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.mplx_plpa3_result_expanded.argtypes = [P, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.mplx_plpa3_result_nodes.argtypes = [P, C.c_uint64] + [C.c_void_p] * 7
+    L.mplx_plpa3_result_entries.argtypes = [P, C.c_uint64] + [C.c_void_p] * 4
     _lib = L
     return L

@@ -25,5 +25,7 @@ struct mplx_ctx_ext_view {
   uint32_t node_chunks, edge_chunks;  // pool sizes in chunks
   const uint32_t *node_tables, *edge_tables;  // device: nq x MAX_NODE_CH / nq x MAX_EDGE_CH
   uint64_t plan_epoch;               // plan launches of the context so far
+  mplx::GuardBlock *guard;           // the context's host-coherent launch-guard block (a kernel of another unit that runs between the
+  double deadline_s;                 // context's own launches polls it) and its launch deadline (mplx_set_deadline; <= 0: none)
 };
 int mplx_ctx_ext_view_get(const mplx_ctx *c, mplx_ctx_ext_view *out);

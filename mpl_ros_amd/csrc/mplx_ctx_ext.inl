@@ -132,5 +132,7 @@ int mplx_ctx_ext_view_get(const mplx_ctx *c, mplx_ctx_ext_view *out) {
   out->node_chunks = c->pools.node_chunks; out->edge_chunks = c->pools.edge_chunks;
   out->node_tables = c->d_node_tables; out->edge_tables = c->d_edge_tables;
   out->plan_epoch = c->plan_epoch;
+  out->guard = c->guard;
+  out->deadline_s = c->deadline_s;
   return MPLX_OK;
 }

@@ -12,6 +12,7 @@
 
 #include "mplx_ctx_ext.h"
 #include "mplx_poly3.h"
+#include "mplx_poly3_lpa_host.h"
 #include "mplx_poly3_space.h"
 
 using namespace mplx;
@@ -398,6 +399,24 @@ int mplx_poly3_space_internal_view(mplx_poly3 *p, mplx_poly3_space_view *out) {
   return MPLX_OK;
 }
 int mplx_poly3_space_internal_fail(mplx_poly3 *p, int code, const char *msg) { return p3fail(p, code, "%s", msg); }
+// (internal: mplx_poly3_lpa_host.h) the view the LPA* works with
+int mplx_poly3_lpa_internal_view(mplx_poly3 *p, mplx_poly3_lpa_view *out) {
+  if (!p || !out) return MPLX_ERR_ARG;
+  if (!p->have_cfg) return p3fail(p, MPLX_ERR_ARG, "mplx_poly3_config first");
+  if (!p->committed) return p3fail(p, MPLX_ERR_ARG, "mplx_poly3_commit first");
+  mplx_ctx_ext_view V;
+  if (mplx_ctx_ext_view_get(p->ctx, &V) != MPLX_OK) return p3fail(p, MPLX_ERR_ARG, "internal: no planner context");
+  out->dev = poly3_dev(p);
+  out->general = poly3_general(p) ? 1 : 0;
+  out->n_worlds = (int32_t)p->worlds.size();
+  out->device = p->device;
+  out->stream = p->stream;
+  out->guard = V.guard;
+  out->deadline_s = V.deadline_s;
+  out->commit_epoch = p->commit_epoch;
+  out->cfg_epoch = p->cfg_epoch;
+  return MPLX_OK;
+}
 // plan launches of the handle so far (a wrapper that shares the handle notices that somebody else planned on it since)
 extern "C" uint64_t mplx_poly3_plan_epoch(const mplx_poly3 *p) {
   mplx_ctx_ext_view V;

@@ -86,6 +86,139 @@ def jrk_segs(p0, v0, a0, us, dt):
     return np.array(rows).reshape(-1, 19)
 
 
+U27 = control_lattice(1.0, 1)  # the 27-input lattice: every axis -1, 0, 1
+
+# (centre at t = 0, velocity) of the moving cubes of replanner_world3
+REPLANNER_OBS3 = [((6, 12, 1.5), (0, -0.6, 0)), ((10, 6, 2.5), (0, 0.5, 0)), ((13, 14, 2), (-0.3, -0.7, 0)), ((16, 9, 1.25), (0, 0.4, 0.1)),
+                  ((8, 9.5, 2.75), (0.4, 0.0, -0.1))]
+
+
+def replanner_world3(t, turn=False):
+    """Synthetic 3-D world of the replanner flow (setLinearObstacles(obstacles as they are at t) + setStartTime(t) per replan), seen
+    at time t: a 20 m x 20 m x 4 m box with five 2 m cubes moving at constant velocity (PolyhedronLinearObstacle3D, cov_v 0.2).  The
+    box is low enough for the cubes to matter and high enough to pass over or under them.  turn: from t = 2 on the last cube moves
+    the other way and the second one stops -- primitives the planner had found free get blocked, blocked ones get free.
+    Start / goal: replanner_endpoints3()."""
+    W = PolyWorld3D((0.0, 0.0, 0.0), (20.0, 20.0, 4.0), start_t=t)
+    cube = box(1.0)
+    for k, (p, v) in enumerate(REPLANNER_OBS3):
+        p, v = np.array(p, float), np.array(v, float)
+        pos = p + v * t
+        if turn and t >= 2.0:
+            if k == 4:
+                pos = p + v * 2.0 - v * (t - 2.0)
+                v = -v
+            if k == 1:
+                pos = p + v * 2.0
+                v = 0 * v
+        W.linear.append(LinearObstacle3D(cube, pos, v, cov_v=0.2))
+    return W
+
+
+def replanner_endpoints3():
+    start = np.zeros(13); start[0], start[1], start[2] = 4.0, 10.0, 2.0
+    goal = np.zeros(13); goal[0], goal[1], goal[2] = 19.0, 10.0, 2.0
+    return start, goal
+
+
+class PolyLpa3D:
+    """PolyMapPlanner3D with setLPAstar(true): a device-resident LPA* state space over the 3-D moving-obstacle environment of ONE
+    world of a PolyTeam3D (mplx_plpa3_*).  PolyLpa (poly_map.py) one for one, states of 13 doubles (pos3 vel3 acc3 jrk3 t).  The flow
+    of the replanner node: team.set_worlds(...) (setLinearObstacles, setStartTime) -> update_nodes() -> plan(start, goal) ->
+    sub_state_space(1)."""
+
+    def __init__(self, team, world=0):
+        self.team, self.lib, self.world = team, team.lib, int(world)
+        self.result = None
+        self.h = None
+        h = C.c_void_p()
+        code = self.lib.mplx_plpa3_create(team.h, C.byref(h))
+        if code != _capi.OK:
+            raise MplxError(f"mplx_plpa3_create failed ({code})")
+        self.h = h
+
+    def __del__(self):
+        try:
+            if self.h:
+                self.lib.mplx_plpa3_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def check(self, code):
+        if code != _capi.OK:
+            raise MplxError(f"mplx error {code}: {self.lib.mplx_plpa3_last_error(self.h).decode()}")
+
+    def set_capacity(self, nodes, edges, open_log):
+        self.check(self.lib.mplx_plpa3_set_capacity(self.h, int(nodes), int(edges), int(open_log)))
+
+    def initialized(self):
+        return bool(self.lib.mplx_plpa3_initialized(self.h))
+
+    def reset(self):
+        self.check(self.lib.mplx_plpa3_reset(self.h))
+
+    def plan(self, start, goal, eps=1.0, tol_pos=0.5, tol_vel=-1.0, max_expand=-1, heur_ignore_dynamics=True):
+        s = np.ascontiguousarray(start, dtype=np.float64); g = np.ascontiguousarray(goal, dtype=np.float64)
+        assert s.size == 13 and g.size == 13, "states are pos3 vel3 acc3 jrk3 t"
+        R = _capi.Result()
+        self.result = None
+        self.check(self.lib.mplx_plpa3_plan(self.h, self.world, s.ctypes.data, g.ctypes.data, float(eps), float(tol_pos), float(tol_vel), int(max_expand),
+                                            int(bool(heur_ignore_dynamics)), C.byref(R)))
+        self.result = R
+        return R.status == _capi.PLAN_OK
+
+    def changed(self):
+        """[(entry, now blocked)] of the last updateNodes, by entry number"""
+        n = C.c_uint64()
+        self.check(self.lib.mplx_plpa3_changed(self.h, 0, None, None, C.byref(n)))
+        e = np.zeros(max(n.value, 1), dtype=np.int32); b = np.zeros(max(n.value, 1), dtype=np.int32)
+        self.check(self.lib.mplx_plpa3_changed(self.h, n.value, e.ctypes.data, b.ctypes.data, C.byref(n)))
+        return list(zip(e[:n.value].tolist(), b[:n.value].tolist()))
+
+    def update_nodes(self):
+        """PolyMapPlanner::updateNodes -> (entries that became blocked, entries that became free, [(entry, now blocked)] by entry number)"""
+        nb, nc = C.c_uint64(), C.c_uint64()
+        self.check(self.lib.mplx_plpa3_update_nodes(self.h, self.world, C.byref(nb), C.byref(nc)))
+        return int(nb.value), int(nc.value), self.changed()
+
+    def sub_state_space(self, time_step):
+        self.check(self.lib.mplx_plpa3_sub_state_space(self.h, self.world, int(time_step)))
+
+    def traj(self):
+        """(actions, node ids, states (n + 1) x 13) of the last successful plan, start -> goal"""
+        n = int(self.lib.mplx_plpa3_traj_len(self.h))
+        act = np.zeros(max(n, 1), dtype=np.int32); ids = np.zeros(n + 1, dtype=np.int32); st = np.zeros((n + 1, 13))
+        if n:
+            self.check(self.lib.mplx_plpa3_result_traj(self.h, act.ctypes.data, ids.ctypes.data, st.ctypes.data))
+        return act[:n], ids[:n + 1] if n else ids[:0], st[:n + 1] if n else st[:0]
+
+    def expanded_ids(self):
+        cap = int(self.result.n_expanded) if self.result is not None else 0
+        ids = np.zeros(max(cap, 1), dtype=np.int32)
+        n = C.c_uint32()
+        self.check(self.lib.mplx_plpa3_result_expanded(self.h, cap, ids.ctypes.data, C.byref(n)))
+        return ids[:n.value]
+
+    def last_kernel_ms(self):
+        ms = C.c_float()
+        self.check(self.lib.mplx_plpa3_last_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def state_space(self):
+        nn, ne = C.c_uint64(), C.c_uint64()
+        self.check(self.lib.mplx_plpa3_counts(self.h, C.byref(nn), C.byref(ne)))
+        n, m = int(nn.value), int(ne.value)
+        states = np.zeros((max(n, 1), 13)); g = np.zeros(max(n, 1)); rhs = np.zeros(max(n, 1)); h = np.zeros(max(n, 1))
+        closed = np.zeros(max(n, 1), dtype=np.int32); opened = closed.copy(); built = closed.copy()
+        self.check(self.lib.mplx_plpa3_result_nodes(self.h, max(n, 1), states.ctypes.data, g.ctypes.data, rhs.ctypes.data, h.ctypes.data, closed.ctypes.data,
+                                                    opened.ctypes.data, built.ctypes.data))
+        child = np.zeros(max(m, 1), dtype=np.int32); parent = child.copy(); action = child.copy(); blocked = child.copy()
+        self.check(self.lib.mplx_plpa3_result_entries(self.h, max(m, 1), child.ctypes.data, parent.ctypes.data, action.ctypes.data, blocked.ctypes.data))
+        return dict(n_nodes=n, states=states[:n], g=g[:n], rhs=rhs[:n], h=h[:n], closed=closed[:n], opened=opened[:n], built=built[:n],
+                    child=child[:m], parent=parent[:m], action=action[:m], blocked=blocked[:m], initialized=self.initialized())
+
+
 class PolyTeam3D:
     """The 3-D worlds of several planners on the device + the shared planner set-up (setVmax/setAmax/setDt/setU/setW)."""
 
@@ -238,6 +371,10 @@ class PolyTeam3D:
         n = C.c_uint32()
         self.check(self.lib.mplx_poly3_result_expanded(self.h, q, cap, ids.ctypes.data, C.byref(n)))
         return ids[:n.value]
+
+    def lpa(self, world=0):
+        """A PolyLpa3D on world `world` of this team: the LPA* planner of the replanner flow (setLPAstar(true), updateNodes, getSubStateSpace)."""
+        return PolyLpa3D(self, world)
 
     def last_kernel_ms(self):
         ms = C.c_float()
