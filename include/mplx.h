@@ -718,6 +718,42 @@ int mplx_plpa3_result_expanded(mplx_plpa3 *l, uint32_t cap, int32_t *ids, uint32
 int mplx_plpa3_result_nodes(mplx_plpa3 *l, uint64_t cap, double *states, double *g, double *rhs, double *h, int32_t *closed, int32_t *opened, int32_t *built);
 /* predecessor entries in creation order, arrays of `cap` entries: child, parent, action, blocked */
 int mplx_plpa3_result_entries(mplx_plpa3 *l, uint64_t cap, int32_t *child, int32_t *parent, int32_t *action, int32_t *blocked);
+/* ---- Fleets of them: N mplx_plpa3 planners on ONE mplx_poly3 handle (its lattice, limits, worlds and obstacles), each bound to a
+ *      world index (members may share a world), whose plan(), updateNodes() and getSubStateSpace() run for all members in ONE launch
+ *      each, one workgroup per member: the multi-robot tick, in which every robot replans against the others' trajectories.
+ *      mplx_plpa_fleet_* one for one, on states of 13 doubles.  A member is an ordinary mplx_plpa3 -- every mplx_plpa3_* getter works
+ *      on it, and so does mplx_plpa3_plan on a single member (one planned that way before the fleet's first device call keeps its
+ *      space) -- owned by the fleet (mplx_plpa3_destroy ignores it).  Per member every result is what the same sequence of
+ *      single-handle calls gives, bit for bit.  A fresh plan runs on the same kernel as a repair, so fresh plans, repairs and re-roots
+ *      of different members share a launch.  n is 1..65535.  At every call, every member's world index is checked against the worlds
+ *      committed now (MPLX_ERR_ARG before any launch), and a member whose space was built before the last mplx_poly3_config drops
+ *      it.  NULL handles answer MPLX_ERR_ARG, an empty string or 0 without touching a device.  Destroy it before the mplx_poly3. ---- */
+typedef struct mplx_plpa3_fleet mplx_plpa3_fleet;
+int mplx_plpa3_fleet_create(mplx_poly3 *p, int32_t n, const int32_t *world_of, mplx_plpa3_fleet **out);  /* no device work */
+void mplx_plpa3_fleet_destroy(mplx_plpa3_fleet *f);
+const char *mplx_plpa3_fleet_last_error(const mplx_plpa3_fleet *f);
+int mplx_plpa3_fleet_size(const mplx_plpa3_fleet *f);
+mplx_plpa3 *mplx_plpa3_fleet_member(mplx_plpa3_fleet *f, int32_t i);  /* borrowed */
+int mplx_plpa3_fleet_set_capacity(mplx_plpa3_fleet *f, uint64_t nodes, uint64_t edges, uint64_t open_log);  /* per member (0 = keep) */
+int mplx_plpa3_fleet_set_world(mplx_plpa3_fleet *f, int32_t i, int32_t world);
+/* plan() of every member i with active[i] != 0 (active NULL: all) from starts[i] to goals[i] (n x 13) in the member's world; out: n
+ * results (zeroed for an inactive member, whose space and stored trajectory stay).  Decided per member as mplx_plpa3_plan decides.  A
+ * per-member outcome (MPLX_PLAN_POOL_FULL, a start outside the map, a start at the goal, the cap reached) ends that member only, with
+ * its own status.  A launch aborted by the deadline invalidates every member that was in it (MPLX_ERR_TIMEOUT). */
+int mplx_plpa3_fleet_plan(mplx_plpa3_fleet *f, const double *starts, const double *goals, const int32_t *active, double eps, double tol_pos, double tol_vel,
+                          int32_t max_expand, int32_t heur_ignore_dynamics, mplx_result *out);
+/* mplx_plpa3_update_nodes of every member that holds a state space, in one launch.  n_blocked / n_cleared (n entries each, or NULL):
+ * per member, 0 for a member without a space; mplx_plpa3_changed on a member answers as after a single call. */
+int mplx_plpa3_fleet_update_nodes(mplx_plpa3_fleet *f, uint64_t *n_blocked, uint64_t *n_cleared);
+/* mplx_plpa3_sub_state_space(member i, time_step[i]) for all members asked in one launch; time_step[i] < 0 leaves the member alone, a
+ * step beyond the member's trajectory is refused.  The members asked must have been planned under one set-up (eps, tolerances, cap,
+ * heuristic mode), as a fleet plan leaves them: otherwise MPLX_ERR_ARG with a message that names both members. */
+int mplx_plpa3_fleet_sub_state_space(mplx_plpa3_fleet *f, const int32_t *time_step);
+/* the last mplx_plpa3_fleet_plan / _sub_state_space: [0] members repaired, [1] search launches that took (1, or 0 when no member ran),
+ * [2] members planned afresh, [3] members skipped (inactive / not asked) */
+int mplx_plpa3_fleet_stats(const mplx_plpa3_fleet *f, uint32_t stats[4]);
+/* kernel time of the last fleet search launch and of the last fleet updateNodes launch */
+int mplx_plpa3_fleet_last_kernel_ms(const mplx_plpa3_fleet *f, float *plan_ms, float *update_ms);
 
 /* ---- after the search: refinement and sampling (host arithmetic, no context, no device) ----
  * TrajSolver3D(control).setWaypoints(wps).setDts(dts).solve(), map_planner_node.cpp:217-227: minimum-derivative

@@ -95,6 +95,9 @@ EXPORTS = [
     "mplx_plpa3_create", "mplx_plpa3_destroy", "mplx_plpa3_last_error", "mplx_plpa3_set_capacity", "mplx_plpa3_initialized", "mplx_plpa3_reset",
     "mplx_plpa3_plan", "mplx_plpa3_update_nodes", "mplx_plpa3_changed", "mplx_plpa3_sub_state_space", "mplx_plpa3_traj_len", "mplx_plpa3_result_traj",
     "mplx_plpa3_last_kernel_ms", "mplx_plpa3_counts", "mplx_plpa3_result_expanded", "mplx_plpa3_result_nodes", "mplx_plpa3_result_entries",
+    "mplx_plpa3_fleet_create", "mplx_plpa3_fleet_destroy", "mplx_plpa3_fleet_last_error", "mplx_plpa3_fleet_size", "mplx_plpa3_fleet_member",
+    "mplx_plpa3_fleet_set_capacity", "mplx_plpa3_fleet_set_world", "mplx_plpa3_fleet_plan", "mplx_plpa3_fleet_update_nodes",
+    "mplx_plpa3_fleet_sub_state_space", "mplx_plpa3_fleet_stats", "mplx_plpa3_fleet_last_kernel_ms",
 ]
 # what include/mplx_poly3_space.h declares (the header mplx.h includes for the state-space export of a 3-D plan)
 EXPORTS_POLY3_SPACE = [
@@ -390,5 +393,20 @@ def load():
     L.mplx_plpa3_result_expanded.argtypes = [P, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     L.mplx_plpa3_result_nodes.argtypes = [P, C.c_uint64] + [C.c_void_p] * 7
     L.mplx_plpa3_result_entries.argtypes = [P, C.c_uint64] + [C.c_void_p] * 4
+    L.mplx_plpa3_fleet_create.argtypes = [P, C.c_int32, C.c_void_p, C.POINTER(P)]
+    L.mplx_plpa3_fleet_destroy.argtypes = [P]
+    L.mplx_plpa3_fleet_destroy.restype = None
+    L.mplx_plpa3_fleet_last_error.argtypes = [P]
+    L.mplx_plpa3_fleet_last_error.restype = C.c_char_p
+    L.mplx_plpa3_fleet_size.argtypes = [P]
+    L.mplx_plpa3_fleet_member.argtypes = [P, C.c_int32]
+    L.mplx_plpa3_fleet_member.restype = P
+    L.mplx_plpa3_fleet_set_capacity.argtypes = [P, C.c_uint64, C.c_uint64, C.c_uint64]
+    L.mplx_plpa3_fleet_set_world.argtypes = [P, C.c_int32, C.c_int32]
+    L.mplx_plpa3_fleet_plan.argtypes = [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.POINTER(Result)]
+    L.mplx_plpa3_fleet_update_nodes.argtypes = [P, C.c_void_p, C.c_void_p]
+    L.mplx_plpa3_fleet_sub_state_space.argtypes = [P, C.c_void_p]
+    L.mplx_plpa3_fleet_stats.argtypes = [P, C.c_void_p]
+    L.mplx_plpa3_fleet_last_kernel_ms.argtypes = [P, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     _lib = L
     return L

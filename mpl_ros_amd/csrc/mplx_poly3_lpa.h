@@ -40,8 +40,11 @@ __device__ __forceinline__ int plpa3_prim_free(const Poly3Dev &D, const Poly3Wor
 }
 
 // ------------------------------------------------------------------ ComputeShortestPath
-template <int CONTROL, bool GEN>
+// FLEET: the plan (fresh or repair) of member blockIdx.x of a fleet (PlpaMember); one workgroup per member, no dependency between
+// them.  What is a member's is replaced before anything reads it; the Poly3Dev and the launch guard are the launch's.
+template <int CONTROL, bool GEN, bool FLEET = false>
 __global__ __launch_bounds__(64) void plpa3_plan_kernel(SearchParams P, PlpaArgs A, Poly3Dev D) {
+  if constexpr (FLEET) plpa_member_args(P, A, A.members[blockIdx.x]);
   constexpr int BLOCK = 64;
   static_assert(CONTROL == CTRL_ACC || CONTROL == CTRL_JRK, "time-keyed states of the moving-obstacle environment");
   constexpr int ns = key_len_c(CONTROL), NK = ns + 1;
@@ -580,8 +583,10 @@ __global__ __launch_bounds__(64) void plpa3_plan_kernel(SearchParams P, PlpaArgs
 // One lane per state: every predecessor entry re-tested against the world as committed now (the primitive rebuilt from the parent
 // record and the action, then isFree(pr, pred.t)); an entry whose outcome changed flips its EDGE_BLOCKED bit and is reported; the
 // look-ahead value of a state whose entries changed is recomputed.  (g values do not change here, so the states are independent.)
-template <int CONTROL, bool GEN>
+// FLEET: the member in blockIdx.y, the grid-stride over blockIdx.x inside it
+template <int CONTROL, bool GEN, bool FLEET = false>
 __global__ __launch_bounds__(64) void plpa3_update_kernel(SearchParams P, PlpaArgs A, Poly3Dev D) {
+  if constexpr (FLEET) plpa_member_args(P, A, A.members[blockIdx.y]);
   constexpr int BLOCK = 64;
   constexpr int ns = key_len_c(CONTROL);
   __shared__ Smem<BLOCK> S;

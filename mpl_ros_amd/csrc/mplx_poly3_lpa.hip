@@ -2,12 +2,11 @@
 // setLPAstar(true), PolyMapPlanner<3>::updateNodes, getSubStateSpace.  mplx_plpa_* (mplx_poly_lpa.hip) one for one, on an mplx_poly3
 // handle, states of 13 doubles (pos3 vel3 acc3 jrk3 t).  Kernels: mplx_poly3_lpa.h.  A translation unit of its own; what it needs of
 // the mplx_poly3 handle comes through mplx_poly3_lpa_internal_view (mplx_poly3_lpa_host.h).  No CPU fallback: every compute entry
-// launches a gfx950 kernel or fails.
+// launches a gfx950 kernel or fails.  The handle and the per-planner host steps are mplx_poly3_lpa_handle.h's, shared with the fleet
+// entries (mplx_poly3_lpa_fleet.hip).
 #include "../../include/mplx.h"
 
 #include <hip/hip_runtime.h>
-
-#include <unistd.h>
 
 #include <algorithm>
 #include <chrono>
@@ -18,48 +17,9 @@
 #include <string>
 #include <vector>
 
-#include "mplx_poly3_lpa.h"
-#include "mplx_poly3_lpa_host.h"
+#include "mplx_poly3_lpa_handle.h"
 
 using namespace mplx;
-
-struct mplx_plpa3 {
-  mplx_poly3 *poly = nullptr;
-  std::string err;
-  // capacities and pools (flat, private to the handle: chunk tables are the identity)
-  uint64_t cap_nodes = 1 << 18, cap_edges = 1 << 21, cap_log = 1 << 21;
-  bool pools_valid = false;
-  int pool_control = 0;
-  char *node_pool = nullptr, *edge_pool = nullptr, *open_pool = nullptr;
-  unsigned long long *table = nullptr;
-  uint64_t table_slots = 0;
-  uint32_t *bkt_head = nullptr;
-  LpaState *d_st = nullptr;
-  QueryIn *d_in = nullptr;
-  QueryOut *d_out = nullptr;
-  int32_t *d_traj_nodes = nullptr, *d_traj_actions = nullptr, *d_rec = nullptr;
-  double *d_traj_states = nullptr;
-  uint32_t *d_changed = nullptr, *d_counters = nullptr;
-  double *d_edge_cost = nullptr;
-  uint32_t *d_succ_child = nullptr, *d_succ_entry = nullptr;  // per state x control input (null when that would be too large)
-  int succ_n_u = 0;
-  uint64_t synced_epoch = ~0ull;  // mplx_poly3 commit count the entries' blocked bits were last brought in step with
-  uint64_t cfg_epoch = ~0ull;     // mplx_poly3 config count the space was built under
-  uint32_t cap_rec = 0;
-  // host copies
-  LpaState st{};
-  QueryOut last_out{};
-  bool valid = false;
-  double goal[13] = {0}, eps = 1.0, tol_pos = 0.5, tol_vel = -1.0;
-  int32_t max_expand = -1, heur_ignore_dynamics = 1;
-  int32_t root_key[MAX_KEY + 1] = {0};
-  int traj_len = 0;
-  std::vector<int32_t> traj_nodes, traj_actions;
-  std::vector<double> traj_states;
-  std::vector<uint32_t> changed;
-  float last_ms = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-};
 
 static std::string g_plpa3_create_error;
 
@@ -78,79 +38,6 @@ static int lf(mplx_plpa3 *l, int code, const char *fmt, ...) {
     if (e_ != hipSuccess) return lf(l, MPLX_ERR_HIP, "%s failed: %s", #x, hipGetErrorString(e_));      \
   } while (0)
 
-static uint64_t np2(uint64_t v) {
-  uint64_t p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-static void plpa3_free(mplx_plpa3 *l) {
-  (void)hipFree(l->node_pool); (void)hipFree(l->edge_pool); (void)hipFree(l->open_pool); (void)hipFree(l->table); (void)hipFree(l->bkt_head);
-  (void)hipFree(l->d_st); (void)hipFree(l->d_in); (void)hipFree(l->d_out); (void)hipFree(l->d_counters);
-  (void)hipFree(l->d_traj_nodes); (void)hipFree(l->d_traj_actions);
-  (void)hipFree(l->d_traj_states); (void)hipFree(l->d_changed); (void)hipFree(l->d_rec); (void)hipFree(l->d_edge_cost); (void)hipFree(l->d_succ_child); (void)hipFree(l->d_succ_entry);
-  l->d_edge_cost = nullptr; l->d_succ_child = l->d_succ_entry = nullptr;
-  l->node_pool = l->edge_pool = l->open_pool = nullptr;
-  l->table = nullptr; l->bkt_head = nullptr; l->d_st = nullptr; l->d_in = nullptr; l->d_out = nullptr;
-  l->d_traj_nodes = l->d_traj_actions = l->d_rec = nullptr; l->d_traj_states = nullptr; l->d_changed = l->d_counters = nullptr;
-  l->pools_valid = false;
-}
-static uint64_t chunks_of(uint64_t cap, int log2) { return std::max<uint64_t>(1, (cap + (1u << log2) - 1) >> log2); }
-// pools for this control kind and lattice width (allocated on the first call and after mplx_plpa3_set_capacity)
-static int plpa3_ensure(mplx_plpa3 *l, int control, int n_u) {
-  if (l->pools_valid && l->pool_control == control && l->succ_n_u == n_u) return MPLX_OK;
-  plpa3_free(l);
-  l->valid = false;
-  const uint64_t nch = chunks_of(l->cap_nodes, NODE_CH_LOG), ech = chunks_of(l->cap_edges, EDGE_CH_LOG), och = chunks_of(l->cap_log, OPEN_CH_LOG);
-  if (nch > (uint64_t)MAX_NODE_CH || ech > (uint64_t)MAX_EDGE_CH || och > (uint64_t)MAX_OPEN_CH)
-    return lf(l, MPLX_ERR_ARG, "capacity too large (at most %d node / %d predecessor / %d OPEN-log chunks)", MAX_NODE_CH, MAX_EDGE_CH, MAX_OPEN_CH);
-  l->table_slots = np2(4ull * (nch << NODE_CH_LOG));
-  LH(l, hipMalloc((void **)&l->node_pool, (size_t)(nch << NODE_CH_LOG) * rec_bytes(control)));
-  LH(l, hipMalloc((void **)&l->edge_pool, (size_t)(ech << EDGE_CH_LOG) * EDGE_BYTES));
-  LH(l, hipMalloc((void **)&l->open_pool, (size_t)(och << OPEN_CH_LOG) * OPEN_BYTES));
-  LH(l, hipMalloc((void **)&l->table, (size_t)l->table_slots * sizeof(unsigned long long)));
-  LH(l, hipMalloc((void **)&l->bkt_head, sizeof(uint32_t) * 2 * NB * NSUB));
-  LH(l, hipMemset(l->bkt_head, 0xFF, sizeof(uint32_t) * 2 * NB * NSUB));
-  LH(l, hipMalloc((void **)&l->d_st, sizeof(LpaState)));
-  LH(l, hipMalloc((void **)&l->d_in, sizeof(QueryIn)));
-  LH(l, hipMalloc((void **)&l->d_out, sizeof(QueryOut)));
-  LH(l, hipMalloc((void **)&l->d_counters, sizeof(uint32_t) * 4));
-  LH(l, hipMalloc((void **)&l->d_traj_nodes, sizeof(int32_t) * (MAX_TRAJ + 1)));
-  LH(l, hipMalloc((void **)&l->d_traj_actions, sizeof(int32_t) * MAX_TRAJ));
-  LH(l, hipMalloc((void **)&l->d_traj_states, sizeof(double) * (MAX_TRAJ + 1) * 13));
-  LH(l, hipMalloc((void **)&l->d_changed, sizeof(uint32_t) * (size_t)(ech << EDGE_CH_LOG)));
-  LH(l, hipMalloc((void **)&l->d_edge_cost, sizeof(double) * (size_t)(ech << EDGE_CH_LOG)));
-  l->succ_n_u = n_u;
-  if ((nch << NODE_CH_LOG) * (uint64_t)n_u * 8ull <= (4ull << 30)) {  // (beyond 4 GB the re-expansion shortcut is off: get_succ runs again)
-    LH(l, hipMalloc((void **)&l->d_succ_child, sizeof(uint32_t) * (size_t)(nch << NODE_CH_LOG) * (size_t)n_u));
-    LH(l, hipMalloc((void **)&l->d_succ_entry, sizeof(uint32_t) * (size_t)(nch << NODE_CH_LOG) * (size_t)n_u));
-  }
-  l->cap_rec = (uint32_t)std::min<uint64_t>(l->cap_nodes, 1u << 24);
-  LH(l, hipMalloc((void **)&l->d_rec, sizeof(int32_t) * (size_t)l->cap_rec));
-  l->pool_control = control;
-  l->pools_valid = true;
-  return MPLX_OK;
-}
-static void plpa3_params(const mplx_plpa3 *l, const mplx_poly3_lpa_view &v, SearchParams &P) {
-  P = SearchParams{};
-  P.control = v.dev.control; P.n_u = v.dev.n_u;
-  P.ns = state_len(v.dev.control); P.nk = state_len(v.dev.control);
-  P.dt = v.dev.dt; P.v_max = v.dev.v_max; P.a_max = v.dev.a_max; P.j_max = v.dev.j_max; P.w = v.dev.w;
-  P.eps = l->eps; P.tol_pos = l->tol_pos; P.tol_vel = l->tol_vel; P.tol_acc = -1.0; P.t_max = INFINITY;
-  P.max_expand = l->max_expand; P.heur_ignore_dynamics = l->heur_ignore_dynamics;
-  P.bucket_width = P.w * P.dt > 0 ? P.w * P.dt * 8.0 : 1.0;  // (coarse OPEN bucket; a fine one is 1 / 1024 of it: the 2-D planner's choice)
-  P.node_pool = l->node_pool; P.edge_pool = l->edge_pool; P.open_pool = l->open_pool;
-  P.node_chunks = (uint32_t)chunks_of(l->cap_nodes, NODE_CH_LOG);
-  P.edge_chunks = (uint32_t)chunks_of(l->cap_edges, EDGE_CH_LOG);
-  P.open_chunks = (uint32_t)chunks_of(l->cap_log, OPEN_CH_LOG);
-  P.table = l->table; P.table_mask = l->table_slots - 1;
-  P.bkt_head = l->bkt_head;
-  P.cap_rec = l->cap_rec;
-  P.nq = 1;
-  P.queries = l->d_in; P.out = l->d_out;
-  P.traj_nodes = l->d_traj_nodes; P.traj_actions = l->d_traj_actions; P.traj_states = l->d_traj_states;
-  P.rec_ids = l->d_rec;
-  P.guard = v.guard;
-}
 template <bool GEN>
 static void launch_plan(int control, hipStream_t s, const SearchParams &P, const PlpaArgs &A, const Poly3Dev &D) {
   if (control == CTRL_ACC) hipLaunchKernelGGL((plpa3_plan_kernel<CTRL_ACC, GEN>), dim3(1), dim3(64), 0, s, P, A, D);
@@ -160,29 +47,6 @@ template <bool GEN>
 static void launch_update(int control, int grid, hipStream_t s, const SearchParams &P, const PlpaArgs &A, const Poly3Dev &D) {
   if (control == CTRL_ACC) hipLaunchKernelGGL((plpa3_update_kernel<CTRL_ACC, GEN>), dim3(grid), dim3(64), 0, s, P, A, D);
   else hipLaunchKernelGGL((plpa3_update_kernel<CTRL_JRK, GEN>), dim3(grid), dim3(64), 0, s, P, A, D);
-}
-// wait for the stream with the poly handle's launch deadline (opt-in, counted from `t0`): past it the abort word of the planner
-// context's guard block is raised, which plpa3_plan_kernel polls
-static int plpa3_wait(mplx_plpa3 *l, const mplx_poly3_lpa_view &v, std::chrono::steady_clock::time_point t0, const char *what) {
-  using clk = std::chrono::steady_clock;
-  bool aborted = false;
-  for (;;) {
-    const hipError_t e = hipStreamQuery(v.stream);
-    if (e == hipSuccess) break;
-    if (e != hipErrorNotReady) return lf(l, MPLX_ERR_HIP, "hipStreamQuery failed while waiting for %s: %s", what, hipGetErrorString(e));
-    const double el = std::chrono::duration<double>(clk::now() - t0).count();
-    if (v.deadline_s > 0 && !aborted && el > v.deadline_s && v.guard) {
-      __atomic_store_n(&v.guard->abort, 1u, __ATOMIC_SEQ_CST);
-      aborted = true;
-    }
-    if (aborted && el > v.deadline_s + 10.0) return lf(l, MPLX_ERR_TIMEOUT, "%s did not end within %.1f s of its launch and did not answer the abort word", what, v.deadline_s);
-    usleep(el < 0.05 ? 50 : 250);
-  }
-  if (aborted) {
-    __atomic_store_n(&v.guard->abort, 0u, __ATOMIC_SEQ_CST);
-    return lf(l, MPLX_ERR_TIMEOUT, "%s did not end within %.1f s of its launch and was aborted (results of the launch are void)", what, v.deadline_s);
-  }
-  return MPLX_OK;
 }
 
 extern "C" int mplx_plpa3_create(mplx_poly3 *poly, mplx_plpa3 **out) {
@@ -194,7 +58,7 @@ extern "C" int mplx_plpa3_create(mplx_poly3 *poly, mplx_plpa3 **out) {
   return MPLX_OK;
 }
 extern "C" void mplx_plpa3_destroy(mplx_plpa3 *l) {
-  if (!l) return;
+  if (!l || l->in_fleet) return;  // (a fleet's member is the fleet's to destroy)
   plpa3_free(l);
   if (l->ev0) (void)hipEventDestroy(l->ev0);
   if (l->ev1) (void)hipEventDestroy(l->ev1);
@@ -219,26 +83,11 @@ extern "C" int mplx_plpa3_reset(mplx_plpa3 *l) {
 
 // the handle's view, refused before any launch: not configured / committed, VEL or SNP control, a world index out of range
 static int plpa3_view(mplx_plpa3 *l, int32_t world, mplx_poly3_lpa_view &v) {
-  const int r = mplx_poly3_lpa_internal_view(l->poly, &v);
-  if (r != MPLX_OK) return lf(l, r, "%s", mplx_poly3_last_error(l->poly));
-  if (v.dev.control != CTRL_ACC && v.dev.control != CTRL_JRK)
-    return lf(l, MPLX_ERR_ARG, "the moving-obstacle LPA* runs ACC or JRK states (time-keyed: an SNP state's key would need 13 integers; VEL states have no caller)");
-  if (v.dev.n_u > POLY3_MAX_U) return lf(l, MPLX_ERR_ARG, "at most %d control inputs", POLY3_MAX_U);
+  const int r = plpa3_poly_view(l->poly, &l->err, v);
+  if (r) return r;
   if (world < 0 || world >= v.n_worlds) return lf(l, MPLX_ERR_ARG, "world index out of range");
-  if (l->valid && l->cfg_epoch != v.cfg_epoch) {  // mplx_poly3_config since the space was built: it is dropped
-    l->valid = false;
-    l->traj_len = 0;
-  }
+  plpa3_config_check(l, v);
   return MPLX_OK;
-}
-static void key_of(int control, const double *s13, int32_t *key) {
-  State st{};
-  for (int a = 0; a < 3; a++) {
-    st.p[a] = s13[a]; st.v[a] = s13[3 + a];
-    if (control == CTRL_JRK) st.a[a] = s13[6 + a];
-  }
-  const int n = state_key(control, st, key);
-  key[n] = (int32_t)round(s13[12] / 0.1);
 }
 
 // PlannerBase::plan with setLPAstar(true): repairs and re-uses the state space of the previous plan when the goal and the start
@@ -251,42 +100,27 @@ static int plpa3_plan_impl(mplx_plpa3 *l, int32_t world, const double *start, co
   const int control = v.dev.control;
   if ((r = plpa3_ensure(l, control, v.dev.n_u)) != MPLX_OK) return r;
   if (!l->ev0) { LH(l, hipEventCreate(&l->ev0)); LH(l, hipEventCreate(&l->ev1)); }
-  QueryIn in = QueryIn{};
-  for (int a = 0; a < 3; a++) {
-    in.start.p[a] = start[a]; in.start.v[a] = start[3 + a];
-    in.goal.p[a] = goal[a]; in.goal.v[a] = goal[3 + a];
-    if (control == CTRL_JRK) { in.start.a[a] = start[6 + a]; in.goal.a[a] = goal[6 + a]; }
-  }
-  in.start_t = start[12];
-  in.goal_control = control;
-  int32_t key[MAX_KEY + 1];
-  memset(key, 0, sizeof(key));
-  key_of(control, start, key);
-  bool same_goal = true;
-  for (int i = 0; i < 12; i++) same_goal = same_goal && l->goal[i] == goal[i];
-  const bool fresh = force_fresh || !l->valid || !same_goal || memcmp(key, l->root_key, sizeof(key)) != 0;
+  Plpa3Query q;
+  plpa3_query(l, control, start, goal, force_fresh, q);
+  const bool fresh = q.fresh;
   SearchParams P;
   plpa3_params(l, v, P);
-  PlpaArgs A = PlpaArgs{};
-  A.st = l->d_st; A.fresh = fresh ? 1 : 0; A.world = world; A.edge_cost = l->d_edge_cost;
-  A.succ_child = l->d_succ_child; A.succ_entry = l->d_succ_entry;
-  // the entries are in step with the committed world when the space is new, or when updateNodes ran after the last commit
-  if (fresh) l->synced_epoch = v.commit_epoch;
-  A.trust_entries = (l->synced_epoch == v.commit_epoch && getenv("MPLX_PLPA_NO_REUSE") == nullptr) ? 1 : 0;
+  PlpaArgs A;
+  plpa3_plan_args(l, v, world, fresh, A);
   hipStream_t s = v.stream;
-  LH(l, hipMemcpyAsync(l->d_in, &in, sizeof(QueryIn), hipMemcpyHostToDevice, s));
+  LH(l, hipMemcpyAsync(l->d_in, &q.in, sizeof(QueryIn), hipMemcpyHostToDevice, s));
   if (fresh) {
     LH(l, hipMemsetAsync(l->table, 0xFF, (size_t)l->table_slots * sizeof(unsigned long long), s));
     LH(l, hipMemsetAsync(l->d_st, 0, sizeof(LpaState), s));
   }
-  LH(l, hipStreamSynchronize(s));  // (`in` is a local; the guard block is cleared with no copy in flight)
+  LH(l, hipStreamSynchronize(s));  // (`q` is a local; the guard block is cleared with no copy in flight)
   if (v.guard) memset(v.guard, 0, sizeof(GuardBlock));
   const auto t0 = std::chrono::steady_clock::now();
   LH(l, hipEventRecord(l->ev0, s));
   if (v.general) launch_plan<true>(control, s, P, A, v.dev); else launch_plan<false>(control, s, P, A, v.dev);
   LH(l, hipGetLastError());
   LH(l, hipEventRecord(l->ev1, s));
-  if ((r = plpa3_wait(l, v, t0, "the 3-D moving-obstacle LPA* launch")) != MPLX_OK) {
+  if ((r = plpa3_wait(&l->err, v, t0, "the 3-D moving-obstacle LPA* launch")) != MPLX_OK) {
     l->valid = false;
     l->traj_len = 0;
     return r;
@@ -295,46 +129,12 @@ static int plpa3_plan_impl(mplx_plpa3 *l, int32_t world, const double *start, co
   LH(l, hipMemcpyAsync(&l->st, l->d_st, sizeof(LpaState), hipMemcpyDeviceToHost, s));
   LH(l, hipStreamSynchronize(s));
   LH(l, hipEventElapsedTime(&l->last_ms, l->ev0, l->ev1));
-  const QueryOut &o = l->last_out;
-  if (out) {
-    memset(out, 0, sizeof(*out));
-    out->status = o.status; out->traj_len = o.traj_len; out->cost = o.cost;
-    out->n_expanded = o.n_expanded; out->n_closed = o.n_closed; out->n_nodes = o.n_nodes; out->n_edges = o.n_edges;
-    out->n_primitives = o.n_primitives; out->n_succ = o.n_succ; out->n_succ_finite = o.n_succ_finite;
-    out->n_push = o.n_push; out->n_refill = query_refills(o); out->n_evict = o.n_evict; out->expand_hash = o.expand_hash;
-  }
-  l->traj_len = 0;
-  if (o.status == MPLX_PLAN_POOL_FULL || o.status == MPLX_PLAN_INTERNAL || o.status == MPLX_PLAN_ABORTED) {
-    l->valid = false;
-    // (as mplx_poly3_plan_batch: the same code, and the state space is dropped)
-    if (o.status == MPLX_PLAN_INTERNAL) return lf(l, MPLX_ERR_ARG, "internal: a hyperplane equation of degree > 2 was met by the quadratic-only kernel");
-  } else if (l->st.valid) {
-    l->valid = true;
-    l->cfg_epoch = v.cfg_epoch;
-    for (int i = 0; i < 13; i++) l->goal[i] = goal[i];
-    if (fresh) memcpy(l->root_key, key, sizeof(key));
-  } else if (fresh) {
-    l->valid = false;  // (the start already satisfies the goal, or lies outside the map: no state space was built)
-    for (int i = 0; i < 13; i++) l->goal[i] = goal[i];
-  }
-  if (o.status == MPLX_PLAN_OK && o.traj_len > 0) {
-    const int len = o.traj_len;
-    l->traj_len = len;
-    l->traj_nodes.assign((size_t)len + 1, 0);
-    l->traj_actions.assign((size_t)len, 0);
-    l->traj_states.assign((size_t)(len + 1) * 13, 0.0);
-    LH(l, hipMemcpy(l->traj_nodes.data(), l->d_traj_nodes, sizeof(int32_t) * (size_t)(len + 1), hipMemcpyDeviceToHost));
-    LH(l, hipMemcpy(l->traj_actions.data(), l->d_traj_actions, sizeof(int32_t) * (size_t)len, hipMemcpyDeviceToHost));
-    LH(l, hipMemcpy(l->traj_states.data(), l->d_traj_states, sizeof(double) * (size_t)(len + 1) * 13, hipMemcpyDeviceToHost));
-  }
-  return MPLX_OK;
+  return plpa3_plan_finish(l, q, v.cfg_epoch, goal, out, nullptr);
 }
 extern "C" int mplx_plpa3_plan(mplx_plpa3 *l, int32_t world, const double *start, const double *goal, double eps, double tol_pos, double tol_vel, int32_t max_expand,
                                int32_t heur_ignore_dynamics, mplx_result *out) {
   if (!l || !start || !goal || !out) return lf(l, MPLX_ERR_ARG, "null argument");
-  // a space that was built under another eps / tolerance / heuristic mode is given up
-  if (l->valid && (l->eps != eps || l->tol_pos != tol_pos || l->tol_vel != tol_vel || l->heur_ignore_dynamics != heur_ignore_dynamics)) l->valid = false;
-  l->eps = eps; l->tol_pos = tol_pos; l->tol_vel = tol_vel; l->max_expand = max_expand; l->heur_ignore_dynamics = heur_ignore_dynamics;
+  plpa3_setup(l, eps, tol_pos, tol_vel, max_expand, heur_ignore_dynamics);
   return plpa3_plan_impl(l, world, start, goal, false, out);
 }
 
@@ -352,27 +152,17 @@ extern "C" int mplx_plpa3_update_nodes(mplx_plpa3 *l, int32_t world, uint64_t *n
   LH(l, hipSetDevice(v.device));
   SearchParams P;
   plpa3_params(l, v, P);
-  PlpaArgs A = PlpaArgs{};
-  A.st = l->d_st; A.world = world; A.changed = l->d_changed; A.counters = l->d_counters; A.edge_cost = l->d_edge_cost;
-  A.succ_child = l->d_succ_child; A.succ_entry = l->d_succ_entry;
-  A.changed_cap = (uint32_t)std::min<uint64_t>((uint64_t)P.edge_chunks << EDGE_CH_LOG, 0xFFFFFFF0ull);
+  PlpaArgs A;
+  plpa3_update_args(l, world, P, A);
   hipStream_t s = v.stream;
   LH(l, hipMemsetAsync(l->d_counters, 0, sizeof(uint32_t) * 4, s));
-  const int grid = (int)std::min<uint64_t>(1024, (l->st.n_nodes + 63) / 64 + 1);
+  const int grid = plpa3_update_grid(l);
   if (v.general) launch_update<true>(v.dev.control, grid, s, P, A, v.dev); else launch_update<false>(v.dev.control, grid, s, P, A, v.dev);
   LH(l, hipGetLastError());
   uint32_t ctr[4] = {0, 0, 0, 0};
   LH(l, hipMemcpyAsync(ctr, l->d_counters, sizeof(ctr), hipMemcpyDeviceToHost, s));
   LH(l, hipStreamSynchronize(s));
-  if (ctr[3]) { l->valid = false; return lf(l, MPLX_ERR_ARG, "internal: a hyperplane equation of degree > 2 was met by the quadratic-only kernel"); }
-  l->synced_epoch = v.commit_epoch;  // every entry has just been re-tested against the world as committed now
-  const uint32_t n = std::min(ctr[2], A.changed_cap);
-  l->changed.resize(n);
-  if (n) LH(l, hipMemcpy(l->changed.data(), l->d_changed, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-  std::sort(l->changed.begin(), l->changed.end(), [](uint32_t a, uint32_t b) { return (a & 0x7FFFFFFFu) < (b & 0x7FFFFFFFu); });
-  if (n_blocked) *n_blocked = ctr[0];
-  if (n_cleared) *n_cleared = ctr[1];
-  return MPLX_OK;
+  return plpa3_update_finish(l, ctr, A.changed_cap, v.commit_epoch, n_blocked, n_cleared, nullptr);
 }
 // the entries updateNodes changed, by entry number (entry -> parent state and action: mplx_plpa3_result_entries / _nodes)
 extern "C" int mplx_plpa3_changed(mplx_plpa3 *l, uint64_t cap, int32_t *entry, int32_t *now_blocked, uint64_t *n) {

@@ -127,10 +127,15 @@ class PolyLpa3D:
     of the replanner node: team.set_worlds(...) (setLinearObstacles, setStartTime) -> update_nodes() -> plan(start, goal) ->
     sub_state_space(1)."""
 
-    def __init__(self, team, world=0):
+    def __init__(self, team, world=0, handle=None):
+        """handle: a borrowed mplx_plpa3 (a fleet's member, PolyLpaFleet3D.member): a view that does not own it"""
         self.team, self.lib, self.world = team, team.lib, int(world)
         self.result = None
         self.h = None
+        self.owned = handle is None
+        if handle is not None:
+            self.h = C.c_void_p(handle)
+            return
         h = C.c_void_p()
         code = self.lib.mplx_plpa3_create(team.h, C.byref(h))
         if code != _capi.OK:
@@ -139,7 +144,7 @@ class PolyLpa3D:
 
     def __del__(self):
         try:
-            if self.h:
+            if self.h and self.owned:
                 self.lib.mplx_plpa3_destroy(self.h)
                 self.h = None
         except Exception:
@@ -217,6 +222,94 @@ class PolyLpa3D:
         self.check(self.lib.mplx_plpa3_result_entries(self.h, max(m, 1), child.ctypes.data, parent.ctypes.data, action.ctypes.data, blocked.ctypes.data))
         return dict(n_nodes=n, states=states[:n], g=g[:n], rhs=rhs[:n], h=h[:n], closed=closed[:n], opened=opened[:n], built=built[:n],
                     child=child[:m], parent=parent[:m], action=action[:m], blocked=blocked[:m], initialized=self.initialized())
+
+
+class PolyLpaFleet3D:
+    """N PolyLpa3D planners on ONE PolyTeam3D (its lattice, limits, worlds and obstacles), member i bound to world world_of[i], whose
+    plan(), update_nodes() and sub_state_space() run for all members in one launch each (mplx_plpa3_fleet_*): the fresh plans, the
+    repairs and the re-roots of different members side by side -- the multi-robot tick.  Per member every result is what the same
+    sequence of calls on a PolyLpa3D gives, bit for bit.  PolyLpaFleet (poly_map.py) one for one, states of 13 doubles."""
+
+    def __init__(self, team, world_of):
+        self.team, self.lib = team, team.lib
+        self.world_of = [int(w) for w in world_of]
+        self.n = len(self.world_of)
+        self.h = None
+        self.members = []
+        w = np.ascontiguousarray(self.world_of, dtype=np.int32)
+        h = C.c_void_p()
+        code = self.lib.mplx_plpa3_fleet_create(team.h, self.n, w.ctypes.data, C.byref(h))
+        if code != _capi.OK:
+            raise MplxError(f"mplx_plpa3_fleet_create failed ({code})")
+        self.h = h
+        self.members = [PolyLpa3D(team, self.world_of[i], handle=self.lib.mplx_plpa3_fleet_member(self.h, i)) for i in range(self.n)]
+        self.results = None
+
+    def __del__(self):
+        try:
+            if self.h:
+                for m in self.members:
+                    m.h = None
+                self.lib.mplx_plpa3_fleet_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def check(self, code):
+        if code != _capi.OK:
+            raise MplxError(f"mplx error {code}: {self.lib.mplx_plpa3_fleet_last_error(self.h).decode()}")
+
+    def member(self, i):
+        """member i as a PolyLpa3D (a view: the fleet owns the handle and the view never destroys it)"""
+        return self.members[i]
+
+    def set_capacity(self, nodes, edges, open_log):
+        self.check(self.lib.mplx_plpa3_fleet_set_capacity(self.h, int(nodes), int(edges), int(open_log)))
+
+    def set_world(self, i, world):
+        self.check(self.lib.mplx_plpa3_fleet_set_world(self.h, int(i), int(world)))
+        self.world_of[i] = self.members[i].world = int(world)
+
+    def plan(self, starts, goals, active=None, eps=1.0, tol_pos=0.5, tol_vel=-1.0, max_expand=-1, heur_ignore_dynamics=True):
+        """plan() of every (active) member, one launch; starts / goals: n x 13.  Returns the n results (zeroed for inactive members)."""
+        s = np.ascontiguousarray(starts, dtype=np.float64).reshape(self.n, 13)
+        g = np.ascontiguousarray(goals, dtype=np.float64).reshape(self.n, 13)
+        a = None if active is None else np.ascontiguousarray([1 if x else 0 for x in active], dtype=np.int32)
+        assert a is None or len(a) == self.n
+        R = (_capi.Result * self.n)()
+        try:
+            self.check(self.lib.mplx_plpa3_fleet_plan(self.h, s.ctypes.data, g.ctypes.data, None if a is None else a.ctypes.data, float(eps), float(tol_pos),
+                                                      float(tol_vel), int(max_expand), int(bool(heur_ignore_dynamics)), R))
+        finally:
+            self.results = [R[i] for i in range(self.n)]
+            for i, m in enumerate(self.members):
+                if a is None or a[i]:
+                    m.result = self.results[i]
+        return self.results
+
+    def update_nodes(self):
+        """updateNodes of every member that holds a space, one launch -> per member (n_blocked, n_cleared, [(entry, now blocked)])"""
+        nb = np.zeros(self.n, dtype=np.uint64); nc = np.zeros(self.n, dtype=np.uint64)
+        self.check(self.lib.mplx_plpa3_fleet_update_nodes(self.h, nb.ctypes.data, nc.ctypes.data))
+        return [(int(nb[i]), int(nc[i]), self.members[i].changed()) for i in range(self.n)]
+
+    def sub_state_space(self, steps):
+        """getSubStateSpace(steps[i]) of member i (an int: of every member; < 0 leaves the member alone), one launch"""
+        st = np.ascontiguousarray([int(steps)] * self.n if np.isscalar(steps) else steps, dtype=np.int32)
+        assert len(st) == self.n
+        self.check(self.lib.mplx_plpa3_fleet_sub_state_space(self.h, st.ctypes.data))
+
+    def stats(self):
+        """of the last plan / sub_state_space: [members repaired, search launches, members planned afresh, members skipped]"""
+        st = np.zeros(4, dtype=np.uint32)
+        self.check(self.lib.mplx_plpa3_fleet_stats(self.h, st.ctypes.data))
+        return [int(x) for x in st]
+
+    def last_kernel_ms(self):
+        """(kernel ms of the last search launch, of the last updateNodes launch)"""
+        a, b = C.c_float(), C.c_float()
+        self.check(self.lib.mplx_plpa3_fleet_last_kernel_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
 
 class PolyTeam3D:
@@ -375,6 +468,11 @@ class PolyTeam3D:
     def lpa(self, world=0):
         """A PolyLpa3D on world `world` of this team: the LPA* planner of the replanner flow (setLPAstar(true), updateNodes, getSubStateSpace)."""
         return PolyLpa3D(self, world)
+
+    def lpa_fleet(self, world_of):
+        """A PolyLpaFleet3D of len(world_of) LPA* planners on this team, member i on world world_of[i]: their plan(), update_nodes()
+        and sub_state_space() run in one launch each."""
+        return PolyLpaFleet3D(self, world_of)
 
     def last_kernel_ms(self):
         ms = C.c_float()

@@ -22,6 +22,6 @@ for u in api spec help yaw lpa poly filter; do
   fi
 done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $O/libmplx_$N.so $OBJS $S/mplx_lpa_fleet_launch.o $S/mplx_poly_lpa.o $S/mplx_poly_lpa_fleet.o $S/mplx_cloud.o $S/mplx_poly3.o $S/mplx_poly_space.o $S/mplx_poly3_space.o $S/mplx_host.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $O/libmplx_$N.so $OBJS $S/mplx_lpa_fleet_launch.o $S/mplx_poly_lpa.o $S/mplx_poly_lpa_fleet.o $S/mplx_cloud.o $S/mplx_poly3.o $S/mplx_poly_space.o $S/mplx_poly3_space.o $S/mplx_poly3_lpa.o $S/mplx_poly3_lpa_fleet.o $S/mplx_host.o
 rm -f $O/kv_${N}_*.o
 ls -la $O/libmplx_$N.so
