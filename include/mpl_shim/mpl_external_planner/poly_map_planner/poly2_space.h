@@ -102,7 +102,9 @@ inline bool poly2_space_fetch(mplx_poly *p, int32_t q, uint64_t epoch, const mpl
 }
 
 /// setLPAstar(true) mode: the space of the planner's own LPA* handle as it is now; entries with blocked == 0 are the valid
-/// records, the others the blocked ones
+/// records, the others the blocked ones.  (Through the host-decoded dumps on purpose: at the few hundred states of a replanner
+/// tick their two blocking copies are quicker than the passes of mplx_plpa_export_space / _records, which win from some
+/// thousand states on -- measured, DESIGN 3.6.  The changed primitives of updateNodes() do come from the export.)
 inline bool poly2_space_fetch_lpa(mplx_plpa *l, const mplx_result &res, Poly2Space &out) {
   if (out.fetched) return true;
   out = Poly2Space();

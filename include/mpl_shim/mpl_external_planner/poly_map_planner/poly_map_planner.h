@@ -101,19 +101,18 @@ class PolyMapPlanner : public PlannerBase<Dim, Waypoint<Dim>> {
     uint64_t nb = 0, nc = 0, n = 0;
     if (!lcheck(mplx_plpa_update_nodes(lpa_, 0, &nb, &nc))) return;
     if (!lcheck(mplx_plpa_changed(lpa_, 0, nullptr, nullptr, &n)) || n == 0) return;
-    std::vector<int32_t> entry((size_t)n), now((size_t)n);
-    uint64_t nn = 0, ne = 0;
-    if (!lcheck(mplx_plpa_changed(lpa_, n, entry.data(), now.data(), &n)) || !lcheck(mplx_plpa_counts(lpa_, &nn, &ne))) return;
-    std::vector<double> states((size_t)nn * 9);
-    std::vector<int32_t> parent((size_t)ne), action((size_t)ne);
-    if (!lcheck(mplx_plpa_result_nodes(lpa_, nn, states.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))) return;
-    if (!lcheck(mplx_plpa_result_entries(lpa_, ne, nullptr, parent.data(), action.data(), nullptr))) return;
+    // parent state, action and now-blocked bit of the changed entries, gathered on the device in the order of mplx_plpa_changed:
+    // O(changed) over the bus, where two dumps of the whole space used to be decoded here
+    std::vector<double> states((size_t)n * 9);
+    std::vector<int32_t> action((size_t)n), now((size_t)n);
+    if (!lcheck(mplx_plpa_export_changed(lpa_, n, states.data(), action.data(), now.data(), &n))) return;
+    if (n > (uint64_t)action.size()) n = action.size();
     for (size_t i = 0; i < (size_t)n; i++) {  // the primitive of a changed entry: forward_action(pred_coord, pred_action_id)
-      const double *st = &states[(size_t)parent[(size_t)entry[i]] * 9];
+      const double *st = &states[i * 9];
       Waypoint<Dim> w((Control::Control)lpa_control_);
       for (int k = 0; k < 2; k++) { w.pos(k) = st[k]; w.vel(k) = st[2 + k]; w.acc(k) = st[4 + k]; w.jrk(k) = st[6 + k]; }
       w.t = st[8];
-      const Primitive<Dim> pr(w, this->U_vec_[(size_t)action[(size_t)entry[i]]], this->dt_);
+      const Primitive<Dim> pr(w, this->U_vec_[(size_t)action[i]], this->dt_);
       (now[i] ? blocked_prs_ : cleared_prs_).push_back(pr);
     }
   }

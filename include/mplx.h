@@ -536,6 +536,35 @@ int mplx_plpa_result_expanded(mplx_plpa *l, uint32_t cap, int32_t *ids, uint32_t
  * order: child, parent, action, blocked */
 int mplx_plpa_result_nodes(mplx_plpa *l, uint64_t cap, double *states, double *g, double *rhs, double *h, int32_t *closed, int32_t *opened, int32_t *built);
 int mplx_plpa_result_entries(mplx_plpa *l, uint64_t cap, int32_t *child, int32_t *parent, int32_t *action, int32_t *blocked);
+/* The same state space exported ON THE DEVICE: passes over the handle's pools decode it there, and only the arrays asked for cross the
+ * bus (the two dumps above copy the node pool, 128-160 B per state, twice, and walk every predecessor list on the host).  They run on
+ * the mplx_poly object's stream after the handle's last plan / updateNodes / re-root, each of which has waited for its launch.
+ *   *n (offset[] of the _many forms) always carries the full count.  Any output pointer may be NULL: that output is neither produced
+ *   nor copied.  A handle without a valid space (never planned, reset, dropped by a failed launch, a start at the goal) counts 0 and
+ *   returns MPLX_OK with nothing written.  An inconsistency a pass meets (a predecessor list that leaves the space, an entry outside
+ *   it) is MPLX_ERR_ARG with a text in mplx_plpa_last_error, never silent garbage.
+ * _export_space: per state, in id order, what _result_nodes gives (states x 9 | g rhs h | closed opened built).  cap below the count:
+ *   MPLX_ERR_CAPACITY, nothing written.
+ * _export_records: the entries in creation order, filtered by `which` (0 all, 1 valid only, 2 blocked only; the compaction is stable):
+ *   entry = the record's entry number (its row in which = 0), child / parent = state ids, action (without the blocked bit), blocked.
+ *   At most cap rows are written; cap = 0 is a pure count query.
+ * _export_changed: for every entry of the last updateNodes' changed list, in the order of mplx_plpa_changed: the parent's state row,
+ *   the action, the now-blocked bit -- getBlockedPrimitives / getClearedPrimitives at O(changed).  At most cap rows are written.
+ * _export_ms: kernel time of the handle's last _export_space / _export_records / _export_changed (a _many call: of its first handle).
+ * _export_space_many / _export_records_many: the same for n_handles handles bound to ONE mplx_poly object -- in particular a fleet's
+ *   mplx_plpa_fleet_member(f, i) -- in one launch per pass: the outputs are the members' rows one after the other, member i's at
+ *   offset[i] .. offset[i + 1] (offset holds n_handles + 1 values; cap counts rows of the concatenated arrays; entry, child and
+ *   parent stay member-local numbers).  A NULL array, a NULL entry or handles on different objects: MPLX_ERR_ARG before any launch,
+ *   the text (which names the offending index) in every handle's last error and in mplx_plpa_export_last_error (per thread). */
+int mplx_plpa_export_space(mplx_plpa *l, uint64_t cap, double *states, double *g, double *rhs, double *h, int32_t *closed, int32_t *opened, int32_t *built, uint64_t *n);
+int mplx_plpa_export_records(mplx_plpa *l, int32_t which, uint64_t cap, int32_t *entry, int32_t *child, int32_t *parent, int32_t *action, int32_t *blocked, uint64_t *n);
+int mplx_plpa_export_changed(mplx_plpa *l, uint64_t cap, double *parent_states, int32_t *action, int32_t *now_blocked, uint64_t *n);
+int mplx_plpa_export_ms(const mplx_plpa *l, float ms[3]);
+int mplx_plpa_export_space_many(int32_t n_handles, mplx_plpa *const *l, uint64_t cap, uint64_t *offset, double *states, double *g, double *rhs, double *h,
+                                int32_t *closed, int32_t *opened, int32_t *built);
+int mplx_plpa_export_records_many(int32_t n_handles, mplx_plpa *const *l, int32_t which, uint64_t cap, uint64_t *offset, int32_t *entry, int32_t *child,
+                                  int32_t *parent, int32_t *action, int32_t *blocked);
+const char *mplx_plpa_export_last_error(void); /* of this thread's last refused mplx_plpa_export_* / mplx_plpa3_export_* call */
 /* ---- Fleets of them: N mplx_plpa planners on ONE mplx_poly handle (its lattice, limits, worlds and obstacles), each bound to a world
  *      index (members may share a world), whose plan(), updateNodes() and getSubStateSpace() run for all members at once.  A member is
  *      an ordinary mplx_plpa -- every mplx_plpa_* getter works on it, and so does mplx_plpa_plan on a single member -- owned by the fleet
@@ -718,6 +747,16 @@ int mplx_plpa3_result_expanded(mplx_plpa3 *l, uint32_t cap, int32_t *ids, uint32
 int mplx_plpa3_result_nodes(mplx_plpa3 *l, uint64_t cap, double *states, double *g, double *rhs, double *h, int32_t *closed, int32_t *opened, int32_t *built);
 /* predecessor entries in creation order, arrays of `cap` entries: child, parent, action, blocked */
 int mplx_plpa3_result_entries(mplx_plpa3 *l, uint64_t cap, int32_t *child, int32_t *parent, int32_t *action, int32_t *blocked);
+/* the state space exported on the device: mplx_plpa_export_* one for one, states and parent_states x 13; the _many forms take
+ * handles bound to ONE mplx_poly3 object, in particular mplx_plpa3_fleet_member(f, i) */
+int mplx_plpa3_export_space(mplx_plpa3 *l, uint64_t cap, double *states, double *g, double *rhs, double *h, int32_t *closed, int32_t *opened, int32_t *built, uint64_t *n);
+int mplx_plpa3_export_records(mplx_plpa3 *l, int32_t which, uint64_t cap, int32_t *entry, int32_t *child, int32_t *parent, int32_t *action, int32_t *blocked, uint64_t *n);
+int mplx_plpa3_export_changed(mplx_plpa3 *l, uint64_t cap, double *parent_states, int32_t *action, int32_t *now_blocked, uint64_t *n);
+int mplx_plpa3_export_ms(const mplx_plpa3 *l, float ms[3]);
+int mplx_plpa3_export_space_many(int32_t n_handles, mplx_plpa3 *const *l, uint64_t cap, uint64_t *offset, double *states, double *g, double *rhs, double *h,
+                                 int32_t *closed, int32_t *opened, int32_t *built);
+int mplx_plpa3_export_records_many(int32_t n_handles, mplx_plpa3 *const *l, int32_t which, uint64_t cap, uint64_t *offset, int32_t *entry, int32_t *child,
+                                   int32_t *parent, int32_t *action, int32_t *blocked);
 /* ---- Fleets of them: N mplx_plpa3 planners on ONE mplx_poly3 handle (its lattice, limits, worlds and obstacles), each bound to a
  *      world index (members may share a world), whose plan(), updateNodes() and getSubStateSpace() run for all members in ONE launch
  *      each, one workgroup per member: the multi-robot tick, in which every robot replans against the others' trajectories.

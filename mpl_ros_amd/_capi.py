@@ -77,6 +77,8 @@ EXPORTS = [
     "mplx_poly_last_kernel_ms", "mplx_poly_result_cycles", "mplx_poly_set_helpers", "mplx_poly_last_helpers", "mplx_poly_set_deadline", "mplx_plpa_create", "mplx_plpa_destroy", "mplx_plpa_last_error", "mplx_plpa_set_capacity", "mplx_plpa_initialized", "mplx_plpa_reset",
     "mplx_plpa_plan", "mplx_plpa_update_nodes", "mplx_plpa_changed", "mplx_plpa_sub_state_space", "mplx_plpa_traj_len", "mplx_plpa_result_traj", "mplx_plpa_last_kernel_ms", "mplx_plpa_result_cycles",
     "mplx_plpa_counts", "mplx_plpa_result_expanded", "mplx_plpa_result_nodes", "mplx_plpa_result_entries",
+    "mplx_plpa_export_space", "mplx_plpa_export_records", "mplx_plpa_export_changed", "mplx_plpa_export_ms", "mplx_plpa_export_space_many",
+    "mplx_plpa_export_records_many", "mplx_plpa_export_last_error",
     "mplx_plpa_fleet_create", "mplx_plpa_fleet_destroy", "mplx_plpa_fleet_last_error", "mplx_plpa_fleet_size", "mplx_plpa_fleet_member", "mplx_plpa_fleet_set_capacity",
     "mplx_plpa_fleet_set_world", "mplx_plpa_fleet_plan", "mplx_plpa_fleet_update_nodes", "mplx_plpa_fleet_sub_state_space", "mplx_plpa_fleet_stats",
     "mplx_plpa_fleet_last_kernel_ms",
@@ -95,6 +97,8 @@ EXPORTS = [
     "mplx_plpa3_create", "mplx_plpa3_destroy", "mplx_plpa3_last_error", "mplx_plpa3_set_capacity", "mplx_plpa3_initialized", "mplx_plpa3_reset",
     "mplx_plpa3_plan", "mplx_plpa3_update_nodes", "mplx_plpa3_changed", "mplx_plpa3_sub_state_space", "mplx_plpa3_traj_len", "mplx_plpa3_result_traj",
     "mplx_plpa3_last_kernel_ms", "mplx_plpa3_counts", "mplx_plpa3_result_expanded", "mplx_plpa3_result_nodes", "mplx_plpa3_result_entries",
+    "mplx_plpa3_export_space", "mplx_plpa3_export_records", "mplx_plpa3_export_changed", "mplx_plpa3_export_ms", "mplx_plpa3_export_space_many",
+    "mplx_plpa3_export_records_many",
     "mplx_plpa3_fleet_create", "mplx_plpa3_fleet_destroy", "mplx_plpa3_fleet_last_error", "mplx_plpa3_fleet_size", "mplx_plpa3_fleet_member",
     "mplx_plpa3_fleet_set_capacity", "mplx_plpa3_fleet_set_world", "mplx_plpa3_fleet_plan", "mplx_plpa3_fleet_update_nodes",
     "mplx_plpa3_fleet_sub_state_space", "mplx_plpa3_fleet_stats", "mplx_plpa3_fleet_last_kernel_ms",
@@ -293,6 +297,14 @@ def load():
     L.mplx_plpa_result_expanded.argtypes = [P, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     L.mplx_plpa_result_nodes.argtypes = [P, C.c_uint64] + [C.c_void_p] * 7
     L.mplx_plpa_result_entries.argtypes = [P, C.c_uint64] + [C.c_void_p] * 4
+    L.mplx_plpa_export_space.argtypes = [P, C.c_uint64] + [C.c_void_p] * 7 + [C.POINTER(C.c_uint64)]
+    L.mplx_plpa_export_records.argtypes = [P, C.c_int32, C.c_uint64] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64)]
+    L.mplx_plpa_export_changed.argtypes = [P, C.c_uint64] + [C.c_void_p] * 3 + [C.POINTER(C.c_uint64)]
+    L.mplx_plpa_export_ms.argtypes = [P, C.POINTER(C.c_float)]
+    L.mplx_plpa_export_space_many.argtypes = [C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p] + [C.c_void_p] * 7
+    L.mplx_plpa_export_records_many.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p] + [C.c_void_p] * 5
+    L.mplx_plpa_export_last_error.argtypes = []
+    L.mplx_plpa_export_last_error.restype = C.c_char_p
     L.mplx_plpa_fleet_create.argtypes = [P, C.c_int32, C.c_void_p, C.POINTER(P)]
     L.mplx_plpa_fleet_destroy.argtypes = [P]
     L.mplx_plpa_fleet_destroy.restype = None
@@ -393,6 +405,12 @@ def load():
     L.mplx_plpa3_result_expanded.argtypes = [P, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     L.mplx_plpa3_result_nodes.argtypes = [P, C.c_uint64] + [C.c_void_p] * 7
     L.mplx_plpa3_result_entries.argtypes = [P, C.c_uint64] + [C.c_void_p] * 4
+    L.mplx_plpa3_export_space.argtypes = [P, C.c_uint64] + [C.c_void_p] * 7 + [C.POINTER(C.c_uint64)]
+    L.mplx_plpa3_export_records.argtypes = [P, C.c_int32, C.c_uint64] + [C.c_void_p] * 5 + [C.POINTER(C.c_uint64)]
+    L.mplx_plpa3_export_changed.argtypes = [P, C.c_uint64] + [C.c_void_p] * 3 + [C.POINTER(C.c_uint64)]
+    L.mplx_plpa3_export_ms.argtypes = [P, C.POINTER(C.c_float)]
+    L.mplx_plpa3_export_space_many.argtypes = [C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p] + [C.c_void_p] * 7
+    L.mplx_plpa3_export_records_many.argtypes = [C.c_int32, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p] + [C.c_void_p] * 5
     L.mplx_plpa3_fleet_create.argtypes = [P, C.c_int32, C.c_void_p, C.POINTER(P)]
     L.mplx_plpa3_fleet_destroy.argtypes = [P]
     L.mplx_plpa3_fleet_destroy.restype = None

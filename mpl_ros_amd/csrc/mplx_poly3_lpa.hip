@@ -60,6 +60,7 @@ extern "C" int mplx_plpa3_create(mplx_poly3 *poly, mplx_plpa3 **out) {
 extern "C" void mplx_plpa3_destroy(mplx_plpa3 *l) {
   if (!l || l->in_fleet) return;  // (a fleet's member is the fleet's to destroy)
   plpa3_free(l);
+  mplx_plpa_space_free(l->space);
   if (l->ev0) (void)hipEventDestroy(l->ev0);
   if (l->ev1) (void)hipEventDestroy(l->ev1);
   delete l;

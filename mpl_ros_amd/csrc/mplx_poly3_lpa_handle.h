@@ -22,6 +22,7 @@
 #include "../../include/mplx.h"
 #include "mplx_poly3_lpa.h"
 #include "mplx_poly3_lpa_host.h"
+#include "mplx_plpa_space.h"
 
 struct mplx_plpa3 {
   mplx_poly3 *poly = nullptr;
@@ -65,6 +66,7 @@ struct mplx_plpa3 {
   std::vector<uint32_t> changed;
   float last_ms = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  mplx_plpa_space *space = nullptr;  // scratch of the state-space exports (mplx_plpa_space.hip)
 };
 
 // the query of one plan() and the decision it starts with

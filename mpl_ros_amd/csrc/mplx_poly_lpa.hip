@@ -169,6 +169,7 @@ extern "C" int mplx_plpa_create(mplx_poly *poly, mplx_plpa **out) {
 extern "C" void mplx_plpa_destroy(mplx_plpa *l) {
   if (!l || l->in_fleet) return;
   plpa_free(l);
+  mplx_plpa_space_free(l->space);
   if (l->ev0) (void)hipEventDestroy(l->ev0);
   if (l->ev1) (void)hipEventDestroy(l->ev1);
   delete l;

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi
+from . import _capi, plpa_space
 from ._capi import MplxError
 
 VEL, ACC, JRK, SNP = _capi.VEL, _capi.ACC, _capi.JRK, _capi.SNP
@@ -525,6 +525,25 @@ class PolyLpa:
         return dict(n_nodes=n, states=states[:n], g=g[:n], rhs=rhs[:n], h=h[:n], closed=closed[:n], opened=opened[:n], built=built[:n],
                     child=child[:m], parent=parent[:m], action=action[:m], blocked=blocked[:m], initialized=self.initialized())
 
+    def space(self):
+        """the dict of state_space(), key for key, decoded ON THE DEVICE (mplx_plpa_export_space / _export_records): only the
+        result arrays cross the bus, not the pools"""
+        return plpa_space.space(self.lib, "plpa", 9, self.h, self.initialized())
+
+    def records(self, which=plpa_space.WHICH_ALL):
+        """the predecessor entries in creation order -- which: 0 all, 1 valid only, 2 blocked only -- as
+        dict(entry, child, parent, action, blocked); entry is the record's row in records(0)"""
+        return plpa_space.records(self.lib, "plpa", self.h, which)
+
+    def changed_primitives(self):
+        """what getBlockedPrimitives / getClearedPrimitives are built from, for the entries of the last update_nodes() in the order
+        of changed(): (parent states n x 9, actions, now-blocked bits) -- gathered on the device, O(changed)"""
+        return plpa_space.changed_primitives(self.lib, "plpa", 9, self.h)
+
+    def export_ms(self):
+        """kernel ms of the last space / records / changed_primitives export that ran on this handle"""
+        return plpa_space.export_ms(self.lib, "plpa", self.h)
+
 
 class PolyLpaFleet:
     """N PolyLpa planners on ONE PolyTeam (its lattice, limits, worlds and obstacles), member i bound to world world_of[i], whose
@@ -562,6 +581,14 @@ class PolyLpaFleet:
     def member(self, i):
         """member i as a PolyLpa (a view: the fleet owns the handle)"""
         return self.members[i]
+
+    def spaces(self, members=None):
+        """space() of every member (or of the listed ones, in that order), one launch per pass for all of them
+        (mplx_plpa_export_space_many / _export_records_many) -> one dict per member"""
+        idx = list(range(self.n)) if members is None else [int(i) for i in members]
+        out, self.last_offsets, self.last_entry_offsets = plpa_space.spaces(self.lib, "plpa", 9, [self.members[i].h for i in idx],
+                                                                             [self.members[i].initialized() for i in idx])
+        return out
 
     def set_capacity(self, nodes, edges, open_log):
         self.check(self.lib.mplx_plpa_fleet_set_capacity(self.h, int(nodes), int(edges), int(open_log)))
