@@ -5,8 +5,10 @@
  * mpl_test_node/src/ellipsoid_planner_node.cpp:64-175 drives it: the constructor, setMap(obs, r, ori, dim), the setters of
  * PlannerBase, plan(start, goal), getTraj / getTrajCost / getCloseSet / getOpenSet.  The cloud is indexed and the search
  * runs on the device (mplx_cloud_*, include/mplx.h); no PCL kd-tree and no host env_cloud are involved.
- * getExpandedNodes() stays empty, as upstream's (env_cloud.h:57 does not record the expanded nodes).  Requests this
- * back-end does not cover -- setPriorTrajectory, setLPAstar(true) -- make plan() fail with a message.
+ * getExpandedNodes() stays empty, as upstream's (env_cloud.h:57 does not record the expanded nodes).
+ * setPriorTrajectory (ellipsoid_planner_node.cpp:135) samples the trajectory on the host (P1 of csrc/mplx_cloud.h) and the
+ * device search aims its heuristic at the samples (mplx_cloud_set_prior).  Requests this back-end does not cover --
+ * setLPAstar(true), a prior trajectory without segments or duration -- make plan() fail with a message.
  */
 #ifndef MPLX_SHIM_ELLIPSOID_PLANNER_H
 #define MPLX_SHIM_ELLIPSOID_PLANNER_H
@@ -49,10 +51,30 @@ class EllipsoidPlanner : public PlannerBase<3, Waypoint3D> {
     has_map_ = check(mplx_cloud_set_map(dev_, (int32_t)obs.size(), pts.empty() ? nullptr : pts.data(), r, o, d));
   }
 
+  /// env_base::set_prior_trajectory with the dt and w in force (the node calls it after setDt and setW): for (t = 0;
+  /// t < T; t += dt) prior.push_back({traj.evaluate(t), w (T - t)}).  The node guards an empty trajectory itself
+  /// (ellipsoid_planner_node.cpp:132); one that reaches this call is refused.
   void setPriorTrajectory(const Trajectory<3> &traj) override {
-    (void)traj;
-    printf(ANSI_COLOR_RED "[EllipsoidPlanner] setPriorTrajectory: prior trajectories are not supported by the mplx back-end; plan() will fail" ANSI_COLOR_RESET "\n");
-    unsupported_ = true;
+    prior_state_.clear();
+    prior_control_.clear();
+    prior_ctg_.clear();
+    const decimal_t T = traj.getTotalTime();
+    if (traj.segs.empty() || !(T > 0) || !(dt_ > 0)) {
+      printf(ANSI_COLOR_RED "[EllipsoidPlanner] setPriorTrajectory: prior trajectories are not supported by the mplx back-end; plan() will fail" ANSI_COLOR_RESET "\n");
+      unsupported_ = true;
+      return;
+    }
+    unsupported_ = false;
+    for (decimal_t t = 0; t < T; t += dt_) {
+      const Waypoint3D p = traj.evaluate(t);
+      for (int k = 0; k < 3; k++) prior_state_.push_back(p.pos(k));
+      for (int k = 0; k < 3; k++) prior_state_.push_back(p.vel(k));
+      for (int k = 0; k < 3; k++) prior_state_.push_back(p.acc(k));
+      for (int k = 0; k < 3; k++) prior_state_.push_back(p.jrk(k));
+      prior_state_.push_back(t);
+      prior_control_.push_back((int32_t)p.control & 15);
+      prior_ctg_.push_back(w_ * (T - t));
+    }
   }
 
   /// PlannerBase::plan(start, goal) (ellipsoid_planner_node.cpp:162): on the device, through mplx_cloud_*
@@ -80,6 +102,11 @@ class EllipsoidPlanner : public PlannerBase<3, Waypoint3D> {
     for (size_t i = 0; i < U_vec_.size(); i++)
       for (int k = 0; k < 3; k++) U[3 * i + k] = U_vec_[i](k);
     if (!check(mplx_cloud_config(dev_, control, (int32_t)U_vec_.size(), U.data(), dt_, v_max_, a_max_, j_max_, w_))) return false;
+    {  // the prior in force (none: cleared), for this and the later plans
+      const int32_t off[2] = {0, (int32_t)prior_ctg_.size()};
+      const int32_t n_sets = prior_ctg_.empty() ? 0 : 1;
+      if (!check(mplx_cloud_set_prior(dev_, n_sets, off, prior_state_.data(), prior_control_.data(), prior_ctg_.data()))) return false;
+    }
     double s[13], g[13];
     for (int k = 0; k < 3; k++) {
       s[k] = start.pos(k); s[3 + k] = start.vel(k); s[6 + k] = start.acc(k); s[9 + k] = start.jrk(k);
@@ -154,6 +181,8 @@ class EllipsoidPlanner : public PlannerBase<3, Waypoint3D> {
   mplx_cloud *dev_ = nullptr;
   bool has_map_ = false;
   mplx_result res_ = mplx_result();
+  std::vector<double> prior_state_, prior_ctg_;  // the sampled prior trajectory: 13 doubles and a cost-to-go per entry
+  std::vector<int32_t> prior_control_;
   vec_Vec3f close_, open_;
   uint64_t cap_[3] = {1u << 20, 1u << 22, 1u << 21};  // pool capacities: states, predecessor records, OPEN-log entries
 };

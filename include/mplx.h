@@ -671,6 +671,18 @@ int mplx_cloud_set_record(mplx_cloud *c, uint32_t cap_per_query);
 int mplx_cloud_result_expanded(mplx_cloud *c, int32_t q, uint32_t cap, int32_t *ids, uint32_t *n);
 int mplx_cloud_set_deadline(mplx_cloud *c, double seconds); /* launch guard of the search (mplx_set_deadline) */
 int mplx_cloud_last_kernel_ms(const mplx_cloud *c, float *ms);
+/* PlannerBase::setPriorTrajectory, sampled by the caller (P-list of mplx_cloud.h): n_sets tables back to back, set i being
+ * the entries offsets[i] .. offsets[i + 1] - 1 (offsets[0] == 0); per entry a state of 13 doubles (pos3 vel3 acc3 jrk3 t, the
+ * t unused), the control kind of that state and its cost-to-go.  A state created at time t >= 0 with (uint64)(t / dt) below
+ * its query's table length aims its heuristic at that entry and adds the entry's cost-to-go; every other state aims at the
+ * goal.  n_sets == 0 clears the prior; n_sets == 1 guides every query of later batches; otherwise n_sets must equal n of
+ * the next mplx_cloud_plan_batch (MPLX_ERR_ARG there, nothing launched, when it does not) and set i guides query i.  An empty
+ * set: no prior for that query.  The prior stays in force until it is changed.  Values that are not finite: MPLX_ERR_ARG. */
+int mplx_cloud_set_prior(mplx_cloud *c, int32_t n_sets, const int32_t *offsets, const double *states, const int32_t *controls, const double *cost_to_go);
+/* the heuristic of K states (13 doubles each, t included) towards goal (13 doubles) under prior set `set` (0 when no prior is
+ * in force): the parity entry, as mplx_heuristic_batch.  Uses the planner set-up of mplx_cloud_config and the
+ * heur_ignore_dynamics of the last mplx_cloud_plan_batch (0 before the first).  The search itself stores 0 when eps == 0. */
+int mplx_cloud_heuristic_batch(mplx_cloud *c, int32_t K, const double *states, const double *goal, int32_t set, double *h);
 
 /* ---- moving-obstacle environment in 3-D: PolyMapPlanner3D (poly_map_planner.h:107) over env_poly_map<3> / PolyMapUtil<3> /
  *      collide<3> (poly_map_util.h:52-109, primitive_geometry_utils.h, simple_obstacle.h).  mplx_poly_* one for one, with

@@ -90,6 +90,7 @@ EXPORTS = [
     "mplx_cloud_create", "mplx_cloud_destroy", "mplx_cloud_last_error", "mplx_cloud_config", "mplx_cloud_set_map", "mplx_cloud_get_succ_batch",
     "mplx_cloud_last_point_tests", "mplx_cloud_set_capacity", "mplx_cloud_plan_batch", "mplx_cloud_result_traj", "mplx_cloud_result_nodes",
     "mplx_cloud_set_record", "mplx_cloud_result_expanded", "mplx_cloud_set_deadline", "mplx_cloud_last_kernel_ms",
+    "mplx_cloud_set_prior", "mplx_cloud_heuristic_batch",
     "mplx_poly3_create", "mplx_poly3_destroy", "mplx_poly3_last_error", "mplx_poly3_config", "mplx_poly3_begin", "mplx_poly3_set_world",
     "mplx_poly3_add_static", "mplx_poly3_add_linear", "mplx_poly3_add_nonlinear", "mplx_poly3_commit", "mplx_poly3_get_succ_batch",
     "mplx_poly3_set_capacity", "mplx_poly3_plan_batch", "mplx_poly3_result_traj", "mplx_poly3_result_nodes", "mplx_poly3_set_record",
@@ -358,6 +359,8 @@ def load():
     L.mplx_cloud_result_expanded.argtypes = [P, C.c_int32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     L.mplx_cloud_set_deadline.argtypes = [P, C.c_double]
     L.mplx_cloud_last_kernel_ms.argtypes = [P, C.POINTER(C.c_float)]
+    L.mplx_cloud_set_prior.argtypes = [P, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mplx_cloud_heuristic_batch.argtypes = [P, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     L.mplx_poly3_create.argtypes = [C.c_int, C.POINTER(P)]
     L.mplx_poly3_destroy.argtypes = [P]
     L.mplx_poly3_destroy.restype = None

@@ -2,7 +2,8 @@
 //   * a bucketed index of the cloud built on the device (cloud_index_key_kernel / cloud_index_scan_kernel / cloud_index_scatter_kernel),
 //   * env_cloud::get_succ for K states (cloud_get_succ_kernel: the parity entry),
 //   * astar_cloud_kernel: GraphSearch::Astar over env_cloud, one workgroup per query, on the search machinery of
-//     mplx_kernels.h (Smem, OPEN structure, pools, hash table, commit_parallel) and the per-query steps of mplx_search_steps.h.
+//     mplx_kernels.h (Smem, OPEN structure, pools, hash table, commit_parallel) and the per-query steps of mplx_search_steps.h,
+//   * astar_cloud_prior_kernel: the same search with the heuristic guided by a prior trajectory (the P-list below).
 //
 // Index.  Points are bucketed by the cell of edge L = 1.0625 r_f (r_f = (float)r) they fall in; the cell's three integer
 // coordinates are hashed to one of M = next_pow2(n) buckets and the points are counting-sorted by bucket (count, scan,
@@ -47,6 +48,29 @@
 //       (1e300) or whose squared float distance does (1e30), fails dist < r2f in E2, so it blocks nothing and changes
 //       no other decision; its cell coordinate is clamped (NaN to -2^40).  This project's choice: what PCL does with
 //       such a cloud is not known here.
+//
+// P-LIST -- a search guided by a prior trajectory (PlannerBase::setPriorTrajectory, ellipsoid_planner_node.cpp:121-139),
+// followed by the kernel, the shim, the Python front end and the CPU checker (tests/cloud_prior_checker.py).  P1 and P2
+// restate recollections of the un-vendored MPL v1.2.
+//   P1  sampling [UNVERIFIED recollection of env_base::set_prior_trajectory] (host code: the shim and
+//       ellipsoid.prior_from_traj): prior.clear(); T = traj.getTotalTime(); for (t = 0; t < T; t += dt) prior.push_back(
+//       {traj.evaluate(t), w (T - t)}), with the dt and w in force at the call and t accumulated by repeated f64
+//       addition.  An entry's control kind is the low four bits of the evaluated waypoint's control.
+//   P2  get_heur(state) [UNVERIFIED recollection of env_base::get_heur]: 0 when the state's key equals the goal's; else,
+//       with a prior of n entries, t = state.t >= 0 and id = (uint64)(t / dt) < n:
+//       cal_heur(state -> prior[id].state, target control prior[id].control) + prior[id].cost_to_go; else
+//       cal_heur(state -> goal).  A negative or NaN t takes the goal branch; so does a quotient at or past n, however large
+//       (the comparison is made on the f64 quotient: floor(x) < n iff x < n for x >= 0).  heur_ignore_dynamics applies
+//       to cal_heur as ever, on the target's position; eps == 0 gives 0.
+//   P3  time is no part of the key: a state's h is computed once, when the state is created, from the time of the arrival
+//       that creates it (the first arrival in sequential A* order, which is the order the commit creates states in).
+//       All successors of one expansion share t = t(expanded) + dt, so they share the prior entry.
+//   P4  the start's h uses start.t: the prior is indexed by absolute state time.
+//   P5  the goal test, t_max, costs, the (f, g, id) order, D6 and recoverTraj are unchanged.  A prior makes the heuristic
+//       inconsistent in general: re-opened states and popped f values below the current bucket are ordinary here.
+// The table of a query (12 state doubles, control kind and cost-to-go per entry) is staged in LDS at query start when it
+// has at most CLOUD_PRIOR_LDS_CAP entries and is read from global memory otherwise; the heuristic reads it through
+// one generic pointer either way, so both paths run the same arithmetic.
 #pragma once
 #include "mplx_kernels.h"
 
@@ -81,7 +105,8 @@ __device__ __forceinline__ uint32_t cloud_bucket(long long ix, long long iy, lon
   return (uint32_t)h & mask;
 }
 
-// ---- index build: key + count, scan, scatter
+// ---- index build: key + count, scan, scatter (plain kernels: one translation unit only, mplx_cloud.hip)
+#ifndef MPLX_CLOUD_SEARCH_ONLY
 __global__ void cloud_index_key_kernel(uint32_t n, const double *__restrict__ pts, double inv_cell, uint32_t mask, uint32_t *__restrict__ bucket, uint32_t *__restrict__ count) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -121,6 +146,8 @@ __global__ void cloud_index_scatter_kernel(uint32_t n, const double *__restrict_
   pf[at] = make_float4((float)x, (float)y, (float)z, 0.0f);
   pd[3 * (size_t)at] = x; pd[3 * (size_t)at + 1] = y; pd[3 * (size_t)at + 2] = z;
 }
+
+#endif  // MPLX_CLOUD_SEARCH_ONLY
 
 // ---- geometry (E1, E4, E5)
 __device__ __forceinline__ bool cloud_in_bbox(const CloudDev &C, double x, double y, double z) {
@@ -342,11 +369,54 @@ __global__ __launch_bounds__(BLOCK) void cloud_get_succ_kernel(SearchParams P, C
   }
 }
 
+// ---- the prior trajectory of a search (P-list)
+constexpr int CLOUD_PRIOR_LDS_CAP = 256;  // entries staged in LDS: 27 KB beside the search's 87 KB, one workgroup per CU either way
+
+struct CloudPriorDev {
+  const int32_t *begin;    // per query: its first entry
+  const int32_t *count;    // per query: its entries (0: no prior)
+  const double *state;     // 12 per entry: pos3 vel3 acc3 jrk3
+  const double *ctg;       // cost-to-go w (T - t)
+  const int32_t *control;  // control kind of the entry
+};
+struct CloudPriorLds {
+  double state[CLOUD_PRIOR_LDS_CAP][12];
+  double ctg[CLOUD_PRIOR_LDS_CAP];
+  int32_t control[CLOUD_PRIOR_LDS_CAP];
+};
+// one query's table, in LDS or in global memory: generic pointers
+struct CloudPriorView {
+  const double *state, *ctg;
+  const int32_t *control;
+  uint32_t n;
+};
+
+// P2.  t: the state's time; dt: the planner's
+__device__ __forceinline__ double cloud_prior_heur(const HeurParams &hp, int control, const State &s, const int32_t *key, int nkey, double t, double dt, const CloudPriorView &R) {
+  if ((control & 15) == (hp.goal_control & 15) && nkey == hp.goal_nkey) {
+    uint32_t diff = 0;
+    for (int i = 0; i < nkey; i++) diff |= (uint32_t)(key[i] ^ hp.goal_key[i]);
+    if (diff == 0u) return 0.0;
+  }
+  if (R.n > 0u && t >= 0.0) {
+    const double x = t / dt;
+    if (x < (double)R.n) {
+      const uint32_t id = (uint32_t)x;
+      State tg;
+      const double *src = R.state + 12 * (size_t)id;
+#pragma unroll
+      for (int i = 0; i < 12; i++) ((double *)&tg)[i] = src[i];
+      return cal_heur_to(hp.w, hp.v_max, hp.heur_ignore_dynamics, control, s, tg, R.control[id]) + R.ctg[id];
+    }
+  }
+  return cal_heur(hp, control, s);
+}
+
 // ---- GraphSearch::Astar over env_cloud: the per-query steps of mplx_search_steps.h around cloud_expand; the start
 // always free (E8), no yaw, no potential.  Keys: the voxel environment's (no time key); order (f, g, id) (D5);
-// a closed state that improves is re-opened (D6).
-template <int BLOCK, int CONTROL>
-__global__ __launch_bounds__(BLOCK) void astar_cloud_kernel(SearchParams P, CloudDev C) {
+// a closed state that improves is re-opened (D6).  PRIOR: the heuristic of the P-list, from the query's table in PR.
+template <int BLOCK, int CONTROL, bool PRIOR>
+__device__ __forceinline__ void astar_cloud_search(const SearchParams &P, const CloudDev &C, const CloudPriorDev &PR) {
   __shared__ Smem<BLOCK> S;
   __shared__ CloudLds<BLOCK> E;
   using V = QView<BLOCK, CONTROL>;
@@ -366,11 +436,30 @@ __global__ __launch_bounds__(BLOCK) void astar_cloud_kernel(SearchParams P, Clou
     const QueryIn &in = P.queries[q];
     const unsigned long long t_begin = wall_clock64();
     query_reset(Q, in, (uint32_t)P.n_u, tid);
+    CloudPriorView R{nullptr, nullptr, nullptr, 0u};
+    if constexpr (PRIOR) {  // (the barrier behind the admission orders the staging stores before the first read)
+      __shared__ CloudPriorLds PL;
+      const uint32_t n = (uint32_t)PR.count[q];
+      const size_t b = (size_t)PR.begin[q];
+      if (n <= (uint32_t)CLOUD_PRIOR_LDS_CAP) {
+        for (uint32_t i = tid; i < 12u * n; i += BLOCK) (&PL.state[0][0])[i] = PR.state[12 * b + i];
+        for (uint32_t i = tid; i < n; i += BLOCK) {
+          PL.ctg[i] = PR.ctg[b + i];
+          PL.control[i] = PR.control[b + i];
+        }
+        R = CloudPriorView{&PL.state[0][0], PL.ctg, PL.control, n};
+      } else {
+        R = CloudPriorView{PR.state + 12 * b, PR.ctg + b, PR.control + b, n};
+      }
+    }
     if (tid == 0) query_admit(Q, in, true, is_goal_state(in.start, in.goal, in.goal_control, P.tol_pos, P.tol_vel, P.tol_acc));  // (E8: the start is always free)
     __syncthreads();
     uint32_t goal_id = NIL;
     if (S.status < 0) {
-      const bool started = query_start<nk, 0>(Q, in, q, tid, 0, 0.0, [&](const int32_t *key) { return get_heur(S.hp, CONTROL, in.start, key, nk); });
+      const bool started = query_start<nk, 0>(Q, in, q, tid, 0, 0.0, [&](const int32_t *key) {
+        if constexpr (PRIOR) return cloud_prior_heur(S.hp, CONTROL, in.start, key, nk, in.start_t, P.dt, R);  // (P4)
+        else return get_heur(S.hp, CONTROL, in.start, key, nk);
+      });
       if (started) for (;;) {
         while (S.n_near + S.reserve > (uint32_t)NC) {
           evict_half(Q, tid);
@@ -406,10 +495,22 @@ __global__ __launch_bounds__(BLOCK) void astar_cloud_kernel(SearchParams P, Clou
         const unsigned long long h64 = act ? key_hash64(L.key, nk) : 0ull;
         dup_probe<BLOCK>(S, act, h64, tid);
         const double lane_cost = act ? S.ucost_lds[tid] : 0.0;
-        if (!S.flag) {
-          commit_parallel<BLOCK, CONTROL, Smem<BLOCK>, nk, false>(Q, tid, q, act, L, h64, lane_cost, (uint32_t)tid);
+        if constexpr (PRIOR) {
+          // (P3) the heuristic of a state this expansion creates: every successor arrives at t(expanded) + dt
+          auto heur = [&](const LaneSucc &l) { return cloud_prior_heur(S.hp, CONTROL, l.tn, l.key, nk, S.cur[0][12] + P.dt, P.dt, R); };
+          using H = decltype(heur);
+          if (!S.flag) {
+            commit_parallel<BLOCK, CONTROL, Smem<BLOCK>, nk, false, NoCreateHook, H>(Q, tid, q, act, L, h64, lane_cost, (uint32_t)tid, false, 0, NoCreateHook(), heur);
+          } else {
+            for (int i = 0; i < P.n_u && S.status < 0; i++)
+              commit_parallel<BLOCK, CONTROL, Smem<BLOCK>, nk, false, NoCreateHook, H>(Q, tid, q, act && tid == i, L, h64, lane_cost, (uint32_t)tid, false, 0, NoCreateHook(), heur);
+          }
         } else {
-          for (int i = 0; i < P.n_u && S.status < 0; i++) commit_parallel<BLOCK, CONTROL, Smem<BLOCK>, nk, false>(Q, tid, q, act && tid == i, L, h64, lane_cost, (uint32_t)tid);
+          if (!S.flag) {
+            commit_parallel<BLOCK, CONTROL, Smem<BLOCK>, nk, false>(Q, tid, q, act, L, h64, lane_cost, (uint32_t)tid);
+          } else {
+            for (int i = 0; i < P.n_u && S.status < 0; i++) commit_parallel<BLOCK, CONTROL, Smem<BLOCK>, nk, false>(Q, tid, q, act && tid == i, L, h64, lane_cost, (uint32_t)tid);
+          }
         }
         __syncthreads();
         if (S.status >= 0) break;  // pool full
@@ -425,4 +526,18 @@ __global__ __launch_bounds__(BLOCK) void astar_cloud_kernel(SearchParams P, Clou
   }
 }
 
+template <int BLOCK, int CONTROL>
+__global__ __launch_bounds__(BLOCK) void astar_cloud_kernel(SearchParams P, CloudDev C) {
+  astar_cloud_search<BLOCK, CONTROL, false>(P, C, CloudPriorDev{});
+}
+// the search guided by prior trajectories: instantiated in mplx_cloud_prior.hip only
+template <int BLOCK, int CONTROL>
+__global__ __launch_bounds__(BLOCK) void astar_cloud_prior_kernel(SearchParams P, CloudDev C, CloudPriorDev PR) {
+  astar_cloud_search<BLOCK, CONTROL, true>(P, C, PR);
+}
+
 }  // namespace mplx
+
+// mplx_cloud_prior.hip: the prior-aware search for P.control (false: no build for it), and P2 for K states
+bool mplx_cloud_prior_launch(int grid, hipStream_t s, const mplx::SearchParams &P, const mplx::CloudDev &D, const mplx::CloudPriorDev &PR);
+void mplx_cloud_heuristic_launch(hipStream_t s, int control, const mplx::HeurParams &hp, double dt, const mplx::CloudPriorView &R, int K, const double *states, double *h);

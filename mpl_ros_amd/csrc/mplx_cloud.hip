@@ -35,6 +35,14 @@ struct mplx_cloud {
   unsigned long long *d_tests = nullptr;
   uint64_t last_tests = 0;
   mplx_ctx *ctx = nullptr;  // pools, batch buffers, guard and result getters of the search
+  // prior trajectories (P-list of mplx_cloud.h): n_sets tables back to back, p_off[n_sets + 1]; persists until changed
+  int n_sets = 0;
+  std::vector<int32_t> p_off;
+  double *d_p_state = nullptr, *d_p_ctg = nullptr;  // 12 doubles / one double per entry
+  int32_t *d_p_ctl = nullptr;
+  int32_t *d_p_begin = nullptr, *d_p_count = nullptr;  // per query of the batch being launched
+  int p_cap_q = 0;
+  int heur_ignore_dynamics = 0;  // of the last mplx_cloud_plan_batch: what mplx_cloud_heuristic_batch uses
 };
 
 static int cfail(mplx_cloud *c, int code, const char *fmt, ...) {
@@ -77,11 +85,19 @@ static void cloud_free_map(mplx_cloud *c) {
   c->d_pf = nullptr; c->d_pd = nullptr; c->d_start = nullptr;
   c->have_map = false;
 }
+static void cloud_free_prior(mplx_cloud *c) {
+  (void)hipFree(c->d_p_state); (void)hipFree(c->d_p_ctg); (void)hipFree(c->d_p_ctl);
+  c->d_p_state = c->d_p_ctg = nullptr; c->d_p_ctl = nullptr;
+  c->n_sets = 0;
+  c->p_off.clear();
+}
 extern "C" void mplx_cloud_destroy(mplx_cloud *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   cloud_free_map(c);
+  cloud_free_prior(c);
+  (void)hipFree(c->d_p_begin); (void)hipFree(c->d_p_count);
   (void)hipFree(c->d_U); (void)hipFree(c->d_ucost); (void)hipFree(c->d_tests);
   mplx_ctx_destroy(c->ctx);
   (void)hipStreamDestroy(c->stream);
@@ -238,16 +254,6 @@ extern "C" int mplx_cloud_set_capacity(mplx_cloud *c, int32_t n_slots, uint64_t 
   return from_ctx(c, mplx_set_capacity(c->ctx, n_slots, total_nodes, total_edges, total_open_log));
 }
 
-static bool launch_search(void *user, int grid, hipStream_t s, const SearchParams &P) {
-  const CloudDev &D = *(const CloudDev *)user;
-  switch (P.control) {
-    case CTRL_VEL: hipLaunchKernelGGL((astar_cloud_kernel<256, CTRL_VEL>), dim3(grid), dim3(256), 0, s, P, D); return true;
-    case CTRL_ACC: hipLaunchKernelGGL((astar_cloud_kernel<256, CTRL_ACC>), dim3(grid), dim3(256), 0, s, P, D); return true;
-    case CTRL_JRK: hipLaunchKernelGGL((astar_cloud_kernel<256, CTRL_JRK>), dim3(grid), dim3(256), 0, s, P, D); return true;
-    case CTRL_SNP: hipLaunchKernelGGL((astar_cloud_kernel<256, CTRL_SNP>), dim3(grid), dim3(256), 0, s, P, D); return true;
-    default: return false;
-  }
-}
 static void to_state(int control, const double *s, State &o) {
   for (int k = 0; k < 3; k++) {
     o.p[k] = s[k];
@@ -256,11 +262,110 @@ static void to_state(int control, const double *s, State &o) {
     o.j[k] = (control & 8) ? s[9 + k] : 0.0;
   }
 }
+struct CloudLaunch {
+  const CloudDev *dev;
+  const CloudPriorDev *prior;  // null: the search without a prior
+};
+static bool launch_search(void *user, int grid, hipStream_t s, const SearchParams &P) {
+  const CloudLaunch &A = *(const CloudLaunch *)user;
+  if (A.prior) return mplx_cloud_prior_launch(grid, s, P, *A.dev, *A.prior);
+  const CloudDev &D = *A.dev;
+  switch (P.control) {
+    case CTRL_VEL: hipLaunchKernelGGL((astar_cloud_kernel<256, CTRL_VEL>), dim3(grid), dim3(256), 0, s, P, D); return true;
+    case CTRL_ACC: hipLaunchKernelGGL((astar_cloud_kernel<256, CTRL_ACC>), dim3(grid), dim3(256), 0, s, P, D); return true;
+    case CTRL_JRK: hipLaunchKernelGGL((astar_cloud_kernel<256, CTRL_JRK>), dim3(grid), dim3(256), 0, s, P, D); return true;
+    case CTRL_SNP: hipLaunchKernelGGL((astar_cloud_kernel<256, CTRL_SNP>), dim3(grid), dim3(256), 0, s, P, D); return true;
+    default: return false;
+  }
+}
+// n_sets tables of 13-double states (the 13th, t, is not used), control kinds and costs-to-go; see include/mplx.h
+extern "C" int mplx_cloud_set_prior(mplx_cloud *c, int32_t n_sets, const int32_t *offsets, const double *states, const int32_t *controls, const double *cost_to_go) {
+  if (!c || n_sets < 0) return cfail(c, MPLX_ERR_ARG, "bad argument");
+  CCHK(c, hipSetDevice(c->device));
+  if (n_sets == 0) {
+    cloud_free_prior(c);
+    return MPLX_OK;
+  }
+  if (!offsets || offsets[0] != 0) return cfail(c, MPLX_ERR_ARG, "set_prior: offsets[0] must be 0");
+  for (int i = 0; i < n_sets; i++)
+    if (offsets[i + 1] < offsets[i]) return cfail(c, MPLX_ERR_ARG, "set_prior: offsets must not decrease (set %d)", i);
+  const size_t m = (size_t)offsets[n_sets];
+  if (m > 0 && (!states || !controls || !cost_to_go)) return cfail(c, MPLX_ERR_ARG, "set_prior: null table");
+  std::vector<double> st(12 * (m ? m : 1));
+  for (size_t e = 0; e < m; e++) {
+    for (int k = 0; k < 13; k++)
+      if (!std::isfinite(states[13 * e + k])) return cfail(c, MPLX_ERR_ARG, "set_prior: entry %zu has a state value that is not finite", e);
+    if (!std::isfinite(cost_to_go[e])) return cfail(c, MPLX_ERR_ARG, "set_prior: entry %zu has a cost-to-go that is not finite", e);
+    const int k4 = controls[e] & 15;
+    if (k4 != CTRL_VEL && k4 != CTRL_ACC && k4 != CTRL_JRK && k4 != CTRL_SNP) return cfail(c, MPLX_ERR_ARG, "set_prior: entry %zu: control kind %d is not one of VEL / ACC / JRK / SNP", e, controls[e]);
+    for (int k = 0; k < 12; k++) st[12 * e + k] = states[13 * e + k];
+  }
+  std::vector<int32_t> ctl(m ? m : 1, 0);
+  for (size_t e = 0; e < m; e++) ctl[e] = controls[e] & 15;
+  cloud_free_prior(c);
+  const size_t ma = m ? m : 1;
+  CCHK(c, hipMalloc((void **)&c->d_p_state, sizeof(double) * 12 * ma));
+  CCHK(c, hipMalloc((void **)&c->d_p_ctg, sizeof(double) * ma));
+  CCHK(c, hipMalloc((void **)&c->d_p_ctl, sizeof(int32_t) * ma));
+  if (m > 0) {
+    CCHK(c, hipMemcpyAsync(c->d_p_state, st.data(), sizeof(double) * 12 * m, hipMemcpyHostToDevice, c->stream));
+    CCHK(c, hipMemcpyAsync(c->d_p_ctg, cost_to_go, sizeof(double) * m, hipMemcpyHostToDevice, c->stream));
+    CCHK(c, hipMemcpyAsync(c->d_p_ctl, ctl.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice, c->stream));
+    CCHK(c, hipStreamSynchronize(c->stream));
+  }
+  c->p_off.assign(offsets, offsets + n_sets + 1);
+  c->n_sets = n_sets;
+  return MPLX_OK;
+}
+
+extern "C" int mplx_cloud_heuristic_batch(mplx_cloud *c, int32_t K, const double *states, const double *goal, int32_t set, double *h) {
+  if (!c || K <= 0 || !states || !goal || !h) return cfail(c, MPLX_ERR_ARG, "bad argument");
+  if (!c->have_cfg) return cfail(c, MPLX_ERR_ARG, "mplx_cloud_config first");
+  if (set < 0 || set >= (c->n_sets > 0 ? c->n_sets : 1)) return cfail(c, MPLX_ERR_ARG, "heuristic_batch: prior set %d of %d", set, c->n_sets);
+  CCHK(c, hipSetDevice(c->device));
+  HeurParams hp{};
+  hp.w = c->w; hp.v_max = c->v_max; hp.heur_ignore_dynamics = c->heur_ignore_dynamics;
+  hp.goal_control = c->control;
+  to_state(c->control, goal, hp.goal);
+  hp.goal_nkey = state_key(c->control, hp.goal, hp.goal_key);
+  CloudPriorView R{nullptr, nullptr, nullptr, 0u};
+  if (c->n_sets > 0) {
+    const size_t b = (size_t)c->p_off[(size_t)set];
+    R = CloudPriorView{c->d_p_state + 12 * b, c->d_p_ctg + b, c->d_p_ctl + b, (uint32_t)(c->p_off[(size_t)set + 1] - c->p_off[(size_t)set])};
+  }
+  std::vector<double> st(13 * (size_t)K);
+  for (int k = 0; k < K; k++) {  // (a state keeps the derivatives its control kind carries, as a query's start does)
+    State s;
+    to_state(c->control, states + 13 * (size_t)k, s);
+    memcpy(&st[13 * (size_t)k], &s, sizeof(double) * 12);
+    st[13 * (size_t)k + 12] = states[13 * (size_t)k + 12];
+  }
+  double *ds = nullptr, *dh = nullptr;
+  CCHK(c, hipMalloc((void **)&ds, sizeof(double) * 13 * (size_t)K));
+  if (hipMalloc((void **)&dh, sizeof(double) * (size_t)K) != hipSuccess) {
+    (void)hipFree(ds);
+    return cfail(c, MPLX_ERR_HIP, "heuristic_batch: out of device memory");
+  }
+  hipError_t e = hipMemcpyAsync(ds, st.data(), sizeof(double) * 13 * (size_t)K, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    mplx_cloud_heuristic_launch(c->stream, c->control, hp, c->dt, R, K, ds, dh);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h, dh, sizeof(double) * (size_t)K, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(ds);
+  (void)hipFree(dh);
+  if (e != hipSuccess) return cfail(c, MPLX_ERR_HIP, "heuristic_batch failed: %s", hipGetErrorString(e));
+  return MPLX_OK;
+}
+
 extern "C" int mplx_cloud_plan_batch(mplx_cloud *c, int32_t n, const double *starts, const double *goals, double eps, double tol_pos, double tol_vel,
                                      double tol_acc, int32_t max_expand, int32_t heur_ignore_dynamics, mplx_result *out) {
   if (!c || n <= 0 || !starts || !goals || !out) return cfail(c, MPLX_ERR_ARG, "bad argument");
   if (!c->have_cfg) return cfail(c, MPLX_ERR_ARG, "mplx_cloud_config first");
   if (!c->have_map) return cfail(c, MPLX_ERR_ARG, "mplx_cloud_set_map first");
+  if (c->n_sets > 1 && c->n_sets != n) return cfail(c, MPLX_ERR_ARG, "plan_batch: %d prior sets are in force for a batch of %d queries (one set, or one per query)", c->n_sets, n);
+  c->heur_ignore_dynamics = heur_ignore_dynamics ? 1 : 0;
   mplx_config g{};
   g.control = c->control;
   g.n_u = c->n_u;
@@ -282,7 +387,31 @@ extern "C" int mplx_cloud_plan_batch(mplx_cloud *c, int32_t n, const double *sta
     q.start_t = starts[13 * (size_t)k + 12];
     q.goal_control = c->control;
   }
-  return from_ctx(c, mplx_ctx_ext_plan(c->ctx, n, in.data(), launch_search, &c->dev, "the point-cloud search launch", out));
+  CloudPriorDev PR{};
+  CloudLaunch A{&c->dev, nullptr};
+  if (c->n_sets > 0) {  // the batch's own view of the tables: one set for every query, or one per query
+    CCHK(c, hipSetDevice(c->device));
+    std::vector<int32_t> bc(2 * (size_t)n);
+    for (int k = 0; k < n; k++) {
+      const size_t s = c->n_sets == 1 ? 0 : (size_t)k;
+      bc[(size_t)k] = c->p_off[s];
+      bc[(size_t)n + (size_t)k] = c->p_off[s + 1] - c->p_off[s];
+    }
+    if (n > c->p_cap_q) {
+      (void)hipFree(c->d_p_begin); (void)hipFree(c->d_p_count);
+      c->d_p_begin = c->d_p_count = nullptr;
+      c->p_cap_q = 0;
+      CCHK(c, hipMalloc((void **)&c->d_p_begin, sizeof(int32_t) * (size_t)n));
+      CCHK(c, hipMalloc((void **)&c->d_p_count, sizeof(int32_t) * (size_t)n));
+      c->p_cap_q = n;
+    }
+    CCHK(c, hipMemcpyAsync(c->d_p_begin, bc.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    CCHK(c, hipMemcpyAsync(c->d_p_count, bc.data() + n, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    CCHK(c, hipStreamSynchronize(c->stream));
+    PR = CloudPriorDev{c->d_p_begin, c->d_p_count, c->d_p_state, c->d_p_ctg, c->d_p_ctl};
+    A.prior = &PR;
+  }
+  return from_ctx(c, mplx_ctx_ext_plan(c->ctx, n, in.data(), launch_search, &A, "the point-cloud search launch", out));
 }
 extern "C" int mplx_cloud_result_traj(mplx_cloud *c, int32_t q, mplx_waypoint *wps, int32_t *actions, int32_t *node_ids) {
   if (!c) return MPLX_ERR_ARG;

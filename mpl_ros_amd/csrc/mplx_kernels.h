@@ -17,6 +17,8 @@
 // Stale entries (node since improved or closed) are dropped at pop time, which yields the same pop
 // sequence as a decrease-key heap.
 #pragma once
+#include <type_traits>
+
 #include "mplx_device.h"
 
 namespace mplx {
@@ -1317,10 +1319,15 @@ __device__ __forceinline__ void open_push(const QView<BLOCK, CONTROL, SM> &Q, ui
 struct NoCreateHook {
   __device__ __forceinline__ void operator()(uint32_t, uint32_t, const LaneSucc &) const {}
 };
-template <int BLOCK, int CONTROL, class SM, int NK = key_len_c(CONTROL), bool YAW = false, class CreateHook = NoCreateHook>
+// heur(L): the heuristic of lane's successor, for a search whose heuristic is not get_heur towards the goal alone (the
+// point-cloud search guided by a prior trajectory, mplx_cloud.h).  GoalHeur, the default, is a tag: the code below is then
+// exactly what it was before the hook existed.
+struct GoalHeur {};
+template <int BLOCK, int CONTROL, class SM, int NK = key_len_c(CONTROL), bool YAW = false, class CreateHook = NoCreateHook, class HeurHook = GoalHeur>
 // have_v0: the caller has already loaded the first table slot of the lane's key (v0_in), e.g. while other work was in flight
 __device__ __forceinline__ void commit_parallel(const QView<BLOCK, CONTROL, SM> &Q, int tid, int q, bool act, const LaneSucc &L, unsigned long long h64, double lane_cost,
-                                                uint32_t action_tag, bool have_v0 = false, unsigned long long v0_in = 0, CreateHook created = CreateHook()) {
+                                                uint32_t action_tag, bool have_v0 = false, unsigned long long v0_in = 0, CreateHook created = CreateHook(),
+                                                HeurHook heur = HeurHook()) {
   using V = QView<BLOCK, CONTROL, SM>;
   const SearchParams &P = Q.P;
   SM &S = Q.S;
@@ -1342,7 +1349,8 @@ __device__ __forceinline__ void commit_parallel(const QView<BLOCK, CONTROL, SM> 
 #ifndef MPLX_NO_HSPEC
   if (act && P.eps != 0.0) {
     // get_heur is 0 when the state's key equals the goal's: with yaw the yaw key is part of that comparison
-    if (YAW && L.yaw_key != S.hp.goal_yaw_key) hspec = cal_heur(S.hp, CONTROL, L.tn);
+    if constexpr (!std::is_same<HeurHook, GoalHeur>::value) hspec = heur(L);
+    else if (YAW && L.yaw_key != S.hp.goal_yaw_key) hspec = cal_heur(S.hp, CONTROL, L.tn);
     else hspec = get_heur(S.hp, CONTROL, L.tn, L.key, nk);
   }
 #endif
@@ -1429,7 +1437,8 @@ __device__ __forceinline__ void commit_parallel(const QView<BLOCK, CONTROL, SM> 
       st[ns] = S.cur[0][12] + P.dt;
     }
 #ifdef MPLX_NO_HSPEC
-    hspec = P.eps == 0.0 ? 0.0 : get_heur(S.hp, CONTROL, L.tn, L.key, nk);
+    if constexpr (!std::is_same<HeurHook, GoalHeur>::value) hspec = P.eps == 0.0 ? 0.0 : heur(L);
+    else hspec = P.eps == 0.0 ? 0.0 : get_heur(S.hp, CONTROL, L.tn, L.key, nk);
 #endif
     hval = hspec;
     V::h(rec) = hval;

@@ -592,18 +592,17 @@ struct HeurParams {
   double goal_yaw;
 };
 
-// min over T >= |dp|_inf / v_max of (optimal-control effort to reach the goal in T) + w T
-MPLX_HD double cal_heur(const HeurParams &hp, int control, const State &s) {
-  const double w = hp.w, v_max = hp.v_max;
-  const State &goal = hp.goal;
+// min over T >= |dp|_inf / v_max of (optimal-control effort to reach the target in T) + w T.  The target is any state
+// with its own control kind: the goal, or a waypoint of a prior trajectory (mplx_cloud.h, P2).
+MPLX_HD double cal_heur_to(double w, double v_max, int heur_ignore_dynamics, int control, const State &s, const State &goal, int goal_control) {
   double dp[3];
   for (int i = 0; i < 3; i++) dp[i] = goal.p[i] - s.p[i];
   // v_max <= 0 is the "unlimited" sentinel (the setters' default, -1): no arrival-time bound exists, so
   // the kinematic term is dropped instead of dividing by a non-positive number
-  if (hp.heur_ignore_dynamics) return v_max > 0 ? w * linf3(s.p, goal.p) / v_max : w * linf3(s.p, goal.p);
+  if (heur_ignore_dynamics) return v_max > 0 ? w * linf3(s.p, goal.p) / v_max : w * linf3(s.p, goal.p);
   const double *v0 = s.v, *v1 = goal.v, *a0 = s.a, *a1 = goal.a;
   double t_bar = v_max > 0 ? linf3(s.p, goal.p) / v_max : 0.0;
-  const int gc = hp.goal_control & 15;  // (the yaw bit does not select another cost-to-go)
+  const int gc = goal_control & 15;  // (the yaw bit does not select another cost-to-go)
   control &= 15;
   if (control == CTRL_JRK && gc == CTRL_JRK) {
     double a0ma1[3] = {a0[0] - a1[0], a0[1] - a1[1], a0[2] - a1[2]};
@@ -644,6 +643,9 @@ MPLX_HD double cal_heur(const HeurParams &hp, int control, const State &s) {
     return (w + 1) * sqrt(dot3(dp, dp));
   }
   return v_max > 0 ? w * sqrt(dot3(dp, dp)) / v_max : w * sqrt(dot3(dp, dp));
+}
+MPLX_HD double cal_heur(const HeurParams &hp, int control, const State &s) {
+  return cal_heur_to(hp.w, hp.v_max, hp.heur_ignore_dynamics, control, s, hp.goal, hp.goal_control);
 }
 
 // get_heur: 0 when the state's key equals the goal's key

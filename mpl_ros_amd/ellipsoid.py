@@ -31,6 +31,75 @@ def control_lattice(u_max, num, use_3d, u_max_z=1.0):
     return np.array([(x, y, z) for x in axis(u_max) for y in axis(u_max) for z in zs], dtype=np.float64)
 
 
+def _poly(c, t):
+    """Primitive1D p, v, a, j at t from the six coefficients, in the shim's expressions (mpl_basis/primitive.h)"""
+    return (c[0] / 120 * t * t * t * t * t + c[1] / 24 * t * t * t * t + c[2] / 6 * t * t * t + c[3] / 2 * t * t + c[4] * t + c[5],
+            c[0] / 24 * t * t * t * t + c[1] / 6 * t * t * t + c[2] / 2 * t * t + c[3] * t + c[4],
+            c[0] / 6 * t * t * t + c[1] / 2 * t * t + c[2] * t + c[3],
+            c[0] / 2 * t * t + c[1] * t + c[2])
+
+
+def prior_from_traj(states, actions, U, control, dt, w, seg_dt=None):
+    """P1 of csrc/mplx_cloud.h on the host, from a get_traj() result: the trajectory is Trajectory<3> of the primitives
+    Primitive<3>(states[i], U[actions[i]], seg_dt) (seg_dt: the dt of the plan that made it, dt by default) and is sampled as
+    env_base::set_prior_trajectory does with the dt and w in force: for (t = 0; t < T; t += dt) {evaluate(t), w (T - t)}.
+    Returns {"states": n x 13, "controls": n, "cost_to_go": n}."""
+    st = np.asarray(states, dtype=np.float64).reshape(-1, 13)
+    U = np.asarray(U, dtype=np.float64).reshape(-1, 3)
+    act = [int(a) for a in actions]
+    seg_dt = float(dt if seg_dt is None else seg_dt)
+    dt, w, kind = float(dt), float(w), int(control) & 15
+    if not dt > 0 or not seg_dt > 0:
+        raise MplxError("prior_from_traj: dt must be > 0")
+    segs = []
+    for i, a in enumerate(act):  # Primitive(p, u, t): the coefficients by control kind
+        p, v, ac, jk = (st[i, 0:3], st[i, 3:6], st[i, 6:9], st[i, 9:12])
+        cs = []
+        for k in range(3):
+            c = [0.0] * 6
+            u = float(U[a, k])
+            if kind == VEL:
+                c[4], c[5] = u, float(p[k])
+            elif kind == ACC:
+                c[3], c[4], c[5] = u, float(v[k]), float(p[k])
+            elif kind == JRK:
+                c[2], c[3], c[4], c[5] = u, float(ac[k]), float(v[k]), float(p[k])
+            else:
+                c[1], c[2], c[3], c[4], c[5] = u, float(jk[k]), float(ac[k]), float(v[k]), float(p[k])
+            cs.append(c)
+        segs.append(cs)
+    taus = [0.0]
+    for _ in segs:
+        taus.append(seg_dt + taus[-1])
+    T = taus[-1] if segs else 0.0
+    out_s, out_c = [], []
+    t = 0.0
+    while t < T:
+        tau = 0.0 if t < 0 else (T if t > T else t)  # Trajectory::evaluate
+        for i in range(len(segs)):
+            if (taus[i] <= tau < taus[i + 1]) or i + 1 == len(segs):
+                x = tau - taus[i]
+                vals = [_poly(segs[i][k], x) for k in range(3)]
+                out_s.append([vals[k][d] for d in range(4) for k in range(3)] + [t])
+                break
+        out_c.append(w * (T - t))
+        t += dt
+    n = len(out_c)
+    return {"states": np.array(out_s, dtype=np.float64).reshape(n, 13), "controls": np.full(n, kind, dtype=np.int32),
+            "cost_to_go": np.array(out_c, dtype=np.float64)}
+
+
+def _prior_arrays(prior):
+    if prior is None:
+        return np.zeros((0, 13)), np.zeros(0, dtype=np.int32), np.zeros(0)
+    st = np.asarray(prior["states"], dtype=np.float64).reshape(-1, 13)
+    ctl = np.asarray(prior["controls"], dtype=np.int32).reshape(-1)
+    ctg = np.asarray(prior["cost_to_go"], dtype=np.float64).reshape(-1)
+    if not (len(st) == len(ctl) == len(ctg)):
+        raise MplxError("prior table: states, controls and cost_to_go must have one length")
+    return st, ctl, ctg
+
+
 class EllipsoidPlanner:
     """MPL::EllipsoidPlanner(verbose) on the device.  Defaults are PlannerBase's."""
 
@@ -48,6 +117,7 @@ class EllipsoidPlanner:
         self.U = None
         self.have_map = False
         self._last = None
+        self._priors = []  # the tables in force on the device (set_priors)
 
     def __del__(self):
         if getattr(self, "h", None) and self.h.value:
@@ -85,8 +155,47 @@ class EllipsoidPlanner:
         SNP with use_jrk; ACC without use_acc)"""
         self.control = int(control)
 
-    def set_prior_trajectory(self, traj):
-        raise MplxError("EllipsoidPlanner.set_prior_trajectory: prior trajectories are not supported by the device back-end")
+    def set_prior_trajectory(self, prior):
+        """PlannerBase::setPriorTrajectory: `prior` is what prior_from_traj returns (the trajectory sampled with the dt and w
+        in force, P1 of csrc/mplx_cloud.h).  It guides every query of the later plans until it is changed; an empty table
+        clears it (clear_prior_trajectory).  None, a trajectory that does not exist, is refused."""
+        if prior is None:
+            raise MplxError("EllipsoidPlanner.set_prior_trajectory: prior trajectories are not supported by the device back-end")
+        self.set_priors([prior])
+
+    def clear_prior_trajectory(self):
+        self.set_priors([])
+
+    def set_priors(self, priors):
+        """mplx_cloud_set_prior: no table (clears), one table for every query, or one per query of the next batches (None or
+        an empty table: no prior for that query)"""
+        tabs = [_prior_arrays(p) for p in priors]
+        if len(tabs) == 1 and len(tabs[0][1]) == 0:
+            tabs = []
+        self._send_priors(tabs)
+        self._priors = tabs
+
+    def _send_priors(self, tabs):
+        if not tabs:
+            self.check(self.lib.mplx_cloud_set_prior(self.h, 0, None, None, None, None))
+            return
+        off = np.zeros(len(tabs) + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(t[1]) for t in tabs])
+        st = np.ascontiguousarray(np.concatenate([t[0] for t in tabs]), dtype=np.float64)
+        ctl = np.ascontiguousarray(np.concatenate([t[1] for t in tabs]), dtype=np.int32)
+        ctg = np.ascontiguousarray(np.concatenate([t[2] for t in tabs]), dtype=np.float64)
+        self.check(self.lib.mplx_cloud_set_prior(self.h, len(tabs), off.ctypes.data, st.ctypes.data if len(ctl) else None,
+                                                 ctl.ctypes.data if len(ctl) else None, ctg.ctypes.data if len(ctl) else None))
+
+    def heuristic_batch(self, states, goal, set=0):
+        """env_base::get_heur (P2) of K states (K x 13, t included) towards `goal` under prior set `set`: the parity entry.
+        heur_ignore_dynamics is the one the last plan ran with."""
+        self._configure()
+        st = np.ascontiguousarray(np.asarray(states, dtype=np.float64).reshape(-1, 13))
+        g = np.ascontiguousarray(np.asarray(goal, dtype=np.float64).reshape(13))
+        h = np.zeros(len(st), dtype=np.float64)
+        self.check(self.lib.mplx_cloud_heuristic_batch(self.h, len(st), st.ctypes.data, g.ctypes.data, int(set), h.ctypes.data))
+        return h
 
     def set_lpastar(self, on):
         if on:
@@ -124,16 +233,26 @@ class EllipsoidPlanner:
     def set_record(self, cap):
         self.check(self.lib.mplx_cloud_set_record(self.h, cap))
 
-    def plan_batch(self, starts, goals):
-        """many queries on the one cloud, one launch: returns the mplx_result dicts"""
+    def plan_batch(self, starts, goals, priors=None):
+        """many queries on the one cloud, one launch: returns the mplx_result dicts.  priors: one table per query (None: no
+        prior for that query) for this batch alone; without it the planner's own prior (set_prior_trajectory) guides all"""
         self._configure()
         s = np.ascontiguousarray(np.asarray(starts, dtype=np.float64).reshape(-1, 13))
         g = np.ascontiguousarray(np.asarray(goals, dtype=np.float64).reshape(-1, 13))
         if len(s) != len(g):
             raise MplxError("plan_batch: as many goals as starts")
         out = (_capi.Result * len(s))()
-        self.check(self.lib.mplx_cloud_plan_batch(self.h, len(s), s.ctypes.data, g.ctypes.data, self.eps, self.tol_pos, self.tol_vel,
-                                                  self.tol_acc, self.max_num, int(self.heur_ignore_dynamics), out))
+        if priors is not None:
+            if len(priors) != len(s):
+                raise MplxError("plan_batch: as many priors as starts")
+            self._send_priors([_prior_arrays(p) for p in priors])
+        try:
+            code = self.lib.mplx_cloud_plan_batch(self.h, len(s), s.ctypes.data, g.ctypes.data, self.eps, self.tol_pos, self.tol_vel,
+                                                  self.tol_acc, self.max_num, int(self.heur_ignore_dynamics), out)
+        finally:
+            if priors is not None:
+                self._send_priors(self._priors)
+        self.check(code)
         self._last = [r.as_dict() for r in out]
         return self._last
 
