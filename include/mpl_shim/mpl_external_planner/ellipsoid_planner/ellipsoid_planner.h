@@ -6,6 +6,7 @@
  * PlannerBase, plan(start, goal), getTraj / getTrajCost / getCloseSet / getOpenSet.  The cloud is indexed and the search
  * runs on the device (mplx_cloud_*, include/mplx.h); no PCL kd-tree and no host env_cloud are involved.
  * getExpandedNodes() stays empty, as upstream's (env_cloud.h:57 does not record the expanded nodes).
+ * getValidPrimitives / getAllPrimitives are served from the device's state-space export (mplx_cloud_result_space*).
  * setPriorTrajectory (ellipsoid_planner_node.cpp:135) samples the trajectory on the host (P1 of csrc/mplx_cloud.h) and the
  * device search aims its heuristic at the samples (mplx_cloud_set_prior).  Requests this back-end does not cover --
  * setLPAstar(true), a prior trajectory without segments or duration -- make plan() fail with a message.
@@ -85,6 +86,7 @@ class EllipsoidPlanner : public PlannerBase<3, Waypoint3D> {
     close_.clear();
     open_.clear();
     res_ = mplx_result();
+    planned_ = false;
     if (use_lpastar_) {
       printf(ANSI_COLOR_RED "[EllipsoidPlanner] plan() refused: LPA* is not supported by the point-cloud back-end" ANSI_COLOR_RESET "\n");
       return false;
@@ -118,6 +120,11 @@ class EllipsoidPlanner : public PlannerBase<3, Waypoint3D> {
       if (!check(mplx_cloud_set_capacity(dev_, 1, cap_[0], cap_[1], cap_[2]))) return false;
       if (!check(mplx_cloud_plan_batch(dev_, 1, s, g, epsilon_, tol_pos_, tol_vel_, tol_acc_, max_num_, heur_ignore_dynamics_ ? 1 : 0, &res_)))
         return false;
+      // the lattice, dt and control kind this state space was built with: what getValidPrimitives / getAllPrimitives rebuild from
+      plan_U_ = U_vec_;
+      plan_dt_ = dt_;
+      plan_control_ = start.control;
+      planned_ = true;
       if (res_.status != MPLX_PLAN_POOL_FULL || attempt >= 6) break;
       for (int k = 0; k < 3; k++) cap_[k] *= 2;  // (the reference grows std containers: grow the device pools and search again)
       printf(ANSI_COLOR_CYAN "[EllipsoidPlanner] device pools exhausted: doubled, planning again" ANSI_COLOR_RESET "\n");
@@ -161,8 +168,42 @@ class EllipsoidPlanner : public PlannerBase<3, Waypoint3D> {
   /// empty, as the reference's: env_cloud::get_succ does not record expanded nodes (env_cloud.h:57)
   vec_Vec3f getExpandedNodes() const override { return vec_Vec3f(); }
   const mplx_result &getResult() const { return res_; }
+  /// PlannerBase::getValidPrimitives / getAllPrimitives: Primitive<3>(parent state, U[action], dt) of every predecessor record of
+  /// the last plan's state space, in record order (for every state in id order its records in arrival order), with the U and dt
+  /// in force at that plan().  States and records come from the device export (mplx_cloud_result_space / _edges of query 0).
+  /// Both return the same list: env_cloud::get_succ SKIPS blocked primitives and never emits them with cost +inf (mplx.h, the
+  /// point-cloud section), so the state space holds no record that is not valid.  Empty when nothing was planned or the plan
+  /// failed before the device; a refused export prints its message.
+  vec_E<Primitive<3>> getValidPrimitives() const override { return device_primitives(); }
+  vec_E<Primitive<3>> getAllPrimitives() const override { return device_primitives(); }
 
  private:
+  vec_E<Primitive<3>> device_primitives() const {
+    vec_E<Primitive<3>> prs;
+    if (!dev_ || !planned_) return prs;
+    const int32_t q = 0;
+    uint64_t node_off[2] = {0, 0}, edge_off[2] = {0, 0};
+    if (!report(mplx_cloud_result_space_counts(dev_, 1, &q, node_off, edge_off))) return prs;
+    const size_t n = (size_t)node_off[1], m = (size_t)edge_off[1];
+    if (n == 0 || m == 0) return prs;
+    std::vector<double> st(13 * n);
+    std::vector<int32_t> parent(m), action(m);
+    if (!report(mplx_cloud_result_space(dev_, 1, &q, n, st.data(), nullptr, nullptr, nullptr, nullptr))) return prs;
+    if (!report(mplx_cloud_result_space_edges(dev_, 1, &q, m, nullptr, parent.data(), action.data()))) return prs;
+    for (size_t i = 0; i < m; i++) {
+      const double *s = &st[13 * (size_t)parent[i]];
+      Waypoint3D w(plan_control_);
+      for (int k = 0; k < 3; k++) { w.pos(k) = s[k]; w.vel(k) = s[3 + k]; w.acc(k) = s[6 + k]; w.jrk(k) = s[9 + k]; }
+      w.t = s[12];
+      prs.push_back(Primitive<3>(w, plan_U_[(size_t)action[i]], plan_dt_));
+    }
+    return prs;
+  }
+  bool report(int code) const {
+    if (code == MPLX_OK) return true;
+    printf(ANSI_COLOR_RED "[EllipsoidPlanner] %s" ANSI_COLOR_RESET "\n", mplx_cloud_last_error(dev_));
+    return false;
+  }
   bool device() {
     if (dev_) return true;
     if (mplx_cloud_create(0, &dev_) != MPLX_OK) {
@@ -184,6 +225,10 @@ class EllipsoidPlanner : public PlannerBase<3, Waypoint3D> {
   std::vector<double> prior_state_, prior_ctg_;  // the sampled prior trajectory: 13 doubles and a cost-to-go per entry
   std::vector<int32_t> prior_control_;
   vec_Vec3f close_, open_;
+  bool planned_ = false;  // the device holds the state space of the last plan()
+  vec_E<VecDf> plan_U_;
+  decimal_t plan_dt_ = 1.0;
+  Control::Control plan_control_ = Control::NONE;
   uint64_t cap_[3] = {1u << 20, 1u << 22, 1u << 21};  // pool capacities: states, predecessor records, OPEN-log entries
 };
 }  // namespace MPL

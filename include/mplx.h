@@ -667,6 +667,10 @@ int mplx_cloud_result_traj(mplx_cloud *c, int32_t q, mplx_waypoint *wps, int32_t
 /* the state space of query q of the last batch (getCloseSet / getOpenSet): n_nodes states in id order with g and their
  * closed / opened flags (a state in OPEN is opened and not closed) */
 int mplx_cloud_result_nodes(mplx_cloud *c, int32_t q, uint64_t cap, mplx_waypoint *coords, double *g, int32_t *closed, int32_t *opened);
+/* the state-space export of a list of queries, for the voxel-map context and for the point-cloud planner (mplx_result_space* /
+ * mplx_cloud_result_space*: states with g, h and flags, predecessor records, from the device pools): declared in a header of its own,
+ * part of this one */
+#include "mplx_space.h"
 int mplx_cloud_set_record(mplx_cloud *c, uint32_t cap_per_query);
 int mplx_cloud_result_expanded(mplx_cloud *c, int32_t q, uint32_t cap, int32_t *ids, uint32_t *n);
 int mplx_cloud_set_deadline(mplx_cloud *c, double seconds); /* launch guard of the search (mplx_set_deadline) */

@@ -108,6 +108,11 @@ EXPORTS = [
 EXPORTS_POLY3_SPACE = [
     "mplx_poly3_result_space", "mplx_poly3_result_edges", "mplx_poly3_result_blocked", "mplx_poly3_result_space_ms", "mplx_poly3_plan_epoch",
 ]
+# what include/mplx_space.h declares (the header mplx.h includes for the state-space export over a list of queries)
+EXPORTS_SPACE = [
+    "mplx_result_space_counts", "mplx_result_space", "mplx_result_space_edges", "mplx_result_space_ms",
+    "mplx_cloud_result_space_counts", "mplx_cloud_result_space", "mplx_cloud_result_space_edges", "mplx_cloud_result_space_ms",
+]
 
 
 class PolySucc(C.Structure):
@@ -429,5 +434,36 @@ def load():
     L.mplx_plpa3_fleet_sub_state_space.argtypes = [P, C.c_void_p]
     L.mplx_plpa3_fleet_stats.argtypes = [P, C.c_void_p]
     L.mplx_plpa3_fleet_last_kernel_ms.argtypes = [P, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    for pre in ("mplx_result_space", "mplx_cloud_result_space"):
+        getattr(L, pre + "_counts").argtypes = [P, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        getattr(L, pre).argtypes = [P, C.c_int32, C.c_void_p, C.c_uint64] + [C.c_void_p] * 5
+        getattr(L, pre + "_edges").argtypes = [P, C.c_int32, C.c_void_p, C.c_uint64] + [C.c_void_p] * 3
+        getattr(L, pre + "_ms").argtypes = [P, C.POINTER(C.c_float)]
     _lib = L
     return L
+
+
+def space_export(lib, handle, check, prefix, width, qs, n_q=None):
+    """The state spaces of the queries `qs` (a list; None: 0 .. n_q - 1) of the handle's last batch through `prefix`_counts / `prefix`
+    / `prefix`_edges (include/mplx_space.h) as numpy arrays, concatenated in the order of qs: states (n x width), g, h, closed, opened,
+    child, parent, action, node_off, edge_off.  `check` raises for a refused call."""
+    import numpy as np
+    if qs is not None:
+        qa = np.ascontiguousarray(np.asarray(qs, dtype=np.int32).reshape(-1))
+        n_q, qp = len(qa), (qa.ctypes.data if len(qa) else None)
+    else:
+        n_q, qp = int(n_q), None
+    node_off = np.zeros(max(n_q, 0) + 1, dtype=np.uint64)
+    edge_off = np.zeros(max(n_q, 0) + 1, dtype=np.uint64)
+    check(getattr(lib, prefix + "_counts")(handle, n_q, qp, node_off.ctypes.data, edge_off.ctypes.data))
+    n, m = int(node_off[-1]), int(edge_off[-1])
+    states = np.zeros((n, width), dtype=np.float64)
+    g, h = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+    closed, opened = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    child, parent, action = (np.zeros(m, dtype=np.int32) for _ in range(3))
+    if n:
+        check(getattr(lib, prefix)(handle, n_q, qp, n, states.ctypes.data, g.ctypes.data, h.ctypes.data, closed.ctypes.data, opened.ctypes.data))
+    if m:
+        check(getattr(lib, prefix + "_edges")(handle, n_q, qp, m, child.ctypes.data, parent.ctypes.data, action.ctypes.data))
+    return dict(states=states, g=g, h=h, closed=closed, opened=opened, child=child, parent=parent, action=action,
+                node_off=node_off.astype(np.int64), edge_off=edge_off.astype(np.int64))

@@ -29,6 +29,10 @@ static_assert(sizeof(State) == 12 * sizeof(double), "State layout");
 
 static std::string g_create_error;
 
+struct mplx_space;
+void mplx_space_free(mplx_space *s);  // (mplx_space.hip, declared in mplx_ctx_ext.h)
+void mplx_space_invalidate(mplx_space *s);
+
 struct mplx_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -134,6 +138,8 @@ struct mplx_ctx {
   unsigned long long filter_mask = 0;
   const char *filter_pool = nullptr;
   uint32_t filter_flag = 0;
+  // device buffers and the cached passes of the state-space export (mplx_space.hip, through mplx_ctx_ext_space_slot); null: none yet
+  struct mplx_space *space = nullptr;
 };
 #define MPLX_REFUSE_PENDING(c)                                                                                                       \
   do {                                                                                                                               \
@@ -231,6 +237,7 @@ extern "C" void mplx_ctx_destroy(mplx_ctx *c) {
   }
   (void)hipStreamSynchronize(c->stream);
   if (c->guard) (void)hipHostFree(c->guard);
+  mplx_space_free(c->space);
   free_pools(c);
   free_batch(c);
   if (c->own_map) (void)hipFree(c->map);
@@ -895,6 +902,9 @@ static std::string guard_dump(const mplx_ctx *c) {
   return out + b;
 }
 static void guard_arm(mplx_ctx *c) {  // before a search launch: no abort pending, no record of an earlier launch
+  // the launch is about to rewrite the pools: the cached passes of a state-space export are dropped HERE, not when the results are
+  // collected -- a call that fails between the launch and the bump of plan_epoch must not leave an export of the old records behind
+  mplx_space_invalidate(c->space);
   if (!c->guard) return;
   memset(c->guard, 0, sizeof(GuardBlock));
   __atomic_thread_fence(__ATOMIC_SEQ_CST);

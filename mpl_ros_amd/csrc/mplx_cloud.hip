@@ -59,6 +59,8 @@ static int cfail(mplx_cloud *c, int code, const char *fmt, ...) {
     hipError_t e__ = (call);                                                                    \
     if (e__ != hipSuccess) return cfail((c), MPLX_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e__)); \
   } while (0)
+mplx_ctx *mplx_cloud_internal_ctx(mplx_cloud *c) { return c ? c->ctx : nullptr; }
+int mplx_cloud_internal_fail(mplx_cloud *c, int code, const char *msg) { return cfail(c, code, "%s", msg); }
 static int from_ctx(mplx_cloud *c, int r) { return r ? cfail(c, r, "%s", mplx_ctx_ext_error(c->ctx)) : MPLX_OK; }
 
 extern "C" int mplx_cloud_create(int device, mplx_cloud **out) {

@@ -127,6 +127,7 @@ int mplx_ctx_ext_view_get(const mplx_ctx *c, mplx_ctx_ext_view *out) {
   out->pools_valid = c->pools_valid ? 1 : 0;
   out->recycled = c->last_recycled ? 1 : 0;
   out->pool_control = c->pool_control;
+  out->last_yaw = c->last_yaw ? 1 : 0;
   out->last_out = c->last_out.data();
   out->node_pool = c->pools.node_pool; out->edge_pool = c->pools.edge_pool;
   out->node_chunks = c->pools.node_chunks; out->edge_chunks = c->pools.edge_chunks;
@@ -136,3 +137,5 @@ int mplx_ctx_ext_view_get(const mplx_ctx *c, mplx_ctx_ext_view *out) {
   out->deadline_s = c->deadline_s;
   return MPLX_OK;
 }
+mplx_space **mplx_ctx_ext_space_slot(mplx_ctx *c) { return c ? &c->space : nullptr; }
+int mplx_ctx_ext_fail(mplx_ctx *c, int code, const char *msg) { return fail(c, code, "%s", msg); }

@@ -16,14 +16,9 @@
 #include <hip/hip_runtime.h>
 
 #include "mplx_device.h"
+#include "mplx_space_common.h"
 
 namespace {
-
-using namespace mplx;
-
-constexpr int TILE = 256;  // nodes per workgroup pass (divides a node chunk: the records of a tile are contiguous)
-static_assert(((1 << NODE_CH_LOG) % TILE) == 0, "a tile must not straddle a node chunk");
-constexpr uint32_t ERR_LIST = 1u, ERR_DEGREE = 2u, ERR_TABLE = 4u;
 
 struct SpaceArgs {
   const char *node_pool, *edge_pool;
@@ -44,22 +39,6 @@ __device__ __forceinline__ const char *space_node(const SpaceArgs &A, uint32_t i
 }
 __device__ __forceinline__ const uint32_t *space_edge(const SpaceArgs &A, uint32_t e) {
   return (const uint32_t *)(A.edge_pool + (((size_t)A.edge_table[e >> EDGE_CH_LOG] << EDGE_CH_LOG) + (e & ((1u << EDGE_CH_LOG) - 1u))) * (size_t)EDGE_BYTES);
-}
-
-// exclusive scan of v over the TILE lanes of the workgroup (LDS buffer sc[TILE]); total in `tot`
-__device__ __forceinline__ uint32_t tile_excl_scan(uint32_t v, uint32_t *sc, int tid, uint32_t &tot) {
-  sc[tid] = v;
-  __syncthreads();
-  for (int d = 1; d < TILE; d <<= 1) {
-    const uint32_t add = tid >= d ? sc[tid - d] : 0u;
-    __syncthreads();
-    sc[tid] += add;
-    __syncthreads();
-  }
-  const uint32_t incl = sc[tid];
-  tot = sc[TILE - 1];
-  __syncthreads();
-  return incl - v;
 }
 
 template <typename ROW>
@@ -156,23 +135,5 @@ __global__ __launch_bounds__(TILE) void space_edges_kernel(SpaceArgs A) {
     }
   }
 }
-
-template <typename T>
-struct Buf {  // a device buffer that grows on demand
-  T *d = nullptr;
-  size_t cap = 0;
-  hipError_t need(size_t n) {
-    if (n <= cap) return hipSuccess;
-    (void)hipFree(d);
-    d = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void **)&d, sizeof(T) * n);
-    if (e == hipSuccess) cap = n;
-    return e;
-  }
-  void release() { (void)hipFree(d); d = nullptr; cap = 0; }
-};
-
-int grid_for(size_t items) { return (int)(items < 4096 ? (items ? items : 1) : 4096); }
 
 }  // namespace

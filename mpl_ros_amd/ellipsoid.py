@@ -291,6 +291,21 @@ class EllipsoidPlanner:
         st = np.array([list(w.pos) + list(w.vel) + list(w.acc) + list(w.jrk) + [w.t] for w in wps[:n]], dtype=np.float64).reshape(n, 13)
         return st, g[:n], cl[:n].astype(bool), op[:n].astype(bool)
 
+    def state_spaces(self, qs=None):
+        """The state spaces of the queries `qs` (None: all) of the last plan_batch, exported on the device in one launch per pass
+        (mplx_cloud_result_space*): a dict of numpy arrays, concatenated in the order of qs -- states (n x 13), g, h, closed, opened
+        per state, child / parent / action per predecessor record (the query's own node ids; for every state in id order its records
+        in arrival order), and node_off / edge_off (len(qs) + 1).  env_cloud skips blocked primitives: every record is a valid one."""
+        if self._last is None:
+            raise MplxError("no plan yet")
+        return _capi.space_export(self.lib, self.h, self.check, "mplx_cloud_result_space", 13, qs, len(self._last))
+
+    def state_space(self, q=0):
+        """state_spaces([q]) without the offsets: the state space of one query."""
+        st = self.state_spaces([int(q)])
+        del st["node_off"], st["edge_off"]
+        return st
+
     def get_close_set(self, q=0):
         st, _, cl, _ = self.nodes(q)
         return st[cl, :3]

@@ -916,6 +916,23 @@ class VoxelMapPlanner:
         return dict(n_nodes=n, n_edges=m, n_blocked_log=int(nb.value), coords=coords, pos=pos, g=g, rhs=rhs, h=h, closed=closed, opened=opened, built=built,
                     child=child[:m], parent=parent[:m], action=action[:m], blocked=blocked[:m])
 
+    def stateSpaces(self, qs=None):
+        """The state spaces of the queries `qs` (None: all) of this planner's last plan() / planBatch() / planBatchWait(), exported on
+        the device in one launch per pass (mplx_result_space*): a dict of numpy arrays, concatenated in the order of qs -- states
+        (n x 14: pos3 vel3 acc3 jrk3 yaw t), g, h, closed, opened per state, child / parent / action per predecessor record (the
+        query's own node ids; for every state in id order its records in arrival order), and node_off / edge_off (len(qs) + 1):
+        query qs[i] owns the rows [node_off[i], node_off[i + 1]) and the records [edge_off[i], edge_off[i + 1])."""
+        if self._use_lpastar:
+            raise MplxError("stateSpaces: an LPA* planner keeps its state space in its own handle -- use lpaStateSpace()")
+        ctx = self._own_results()
+        return _capi.space_export(ctx.lib, ctx.h, ctx.check, "mplx_result_space", 14, qs, len(self._results))
+
+    def stateSpace(self, q=0):
+        """stateSpaces([q]) without the offsets: the state space of one query."""
+        st = self.stateSpaces([int(q)])
+        del st["node_off"], st["edge_off"]
+        return st
+
     def getCloseSet(self):
         _, pos, _, _, closed, _ = self._nodes()
         return pos[closed == 1]
