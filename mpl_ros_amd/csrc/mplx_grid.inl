@@ -21,7 +21,10 @@ __device__ __forceinline__ bool grid_cell_of(const GridDev &g, const double *pt,
   bool in = true;
 #pragma unroll
   for (int i = 0; i < 3; i++) {
-    pn[i] = (int32_t)((pt[i] - g.origin_d[i]) / (double)g.res);  // .cast<int>(): towards zero
+    // .cast<int>(): towards zero.  A quotient that int32 cannot hold, or NaN (a depth sensor's "no return"), is a point
+    // outside: the reference's x86 convert gives INT32_MIN there, the device's convert would give 0 for NaN -- cell 0.
+    const double q = (pt[i] - g.origin_d[i]) / (double)g.res;
+    pn[i] = (q >= -2147483648.0 && q < 2147483648.0) ? (int32_t)q : INT32_MIN;
     in = in && pn[i] >= 0 && pn[i] < g.dim[i];
   }
   return in;

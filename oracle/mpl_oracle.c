@@ -1307,9 +1307,15 @@ void orc_grid_clear(orc_grid *g) {
   memset(g->map, 0, grid_cells(g));
   memset(g->inflated, 0, grid_cells(g));
 }
-/* [IN-TREE voxel_grid.cpp:201-203] ((pt - origin_d_) / res_).cast<int>(): truncation towards zero */
+/* [IN-TREE voxel_grid.cpp:201-203] ((pt - origin_d_) / res_).cast<int>(): truncation towards zero.  A quotient that
+ * int32 cannot hold, or NaN (a depth sensor's "no return"), is undefined in C; the reference, compiled for x86-64, gets
+ * INT32_MIN from the convert instruction, i.e. a point outside the grid.  Stated here explicitly, so that the result does
+ * not depend on the machine the oracle runs on. */
 static void grid_float_to_int(const orc_grid *g, const double *pt, int32_t *pn) {
-  for (int i = 0; i < 3; i++) pn[i] = (int32_t)((pt[i] - g->origin_d[i]) / g->res);
+  for (int i = 0; i < 3; i++) {
+    const double q = (pt[i] - g->origin_d[i]) / g->res;
+    pn[i] = (q >= -2147483648.0 && q < 2147483648.0) ? (int32_t)q : INT32_MIN;
+  }
 }
 static int grid_outside(const orc_grid *g, const int32_t *pn) {
   return pn[0] < 0 || pn[0] >= g->dim[0] || pn[1] < 0 || pn[1] >= g->dim[1] || pn[2] < 0 || pn[2] >= g->dim[2];

@@ -1,12 +1,12 @@
 """VoxelGrid (map ingest): the oracle follows the in-tree voxel_grid.cpp line by line; the CPU
 tests pin it on hand-checked cases, the GPU tests compare the device-resident grid with it bit for bit."""
-import ctypes as C
 import os
 
 import numpy as np
 import pytest
 
 from oracle import orc
+from tests.grid_scenes import RefGrid  # the compiled reference's VoxelGrid (oracle/_ref), shared with test_grid_geometry.py
 
 
 def test_oracle_grid_matches_the_in_tree_semantics():
@@ -44,72 +44,6 @@ def test_oracle_grid_matches_the_in_tree_semantics():
     c2 = g.get_cloud()
     assert len(c2) == 1  # the filled column survives, shifted by the integer origin difference (2, 2)
     assert np.array_equal(g.get_map(), g.get_map(True))
-
-
-class RefGrid:
-    """The reference's own VoxelGrid, compiled from /root/reference/.../voxel_grid.cpp by `make -C oracle ref`
-    (oracle/_ref/libvoxelgrid_ref.so; dependency stand-ins under oracle/ref_stubs)."""
-    PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libvoxelgrid_ref.so")
-
-    def __init__(self, origin, dim, res):
-        L = C.CDLL(self.PATH)
-        D3 = C.c_double * 3
-        L.ref_grid_create.restype = C.c_void_p
-        L.ref_grid_create.argtypes = [D3, D3, C.c_float]
-        for f in ("ref_grid_destroy", "ref_grid_clear", "ref_grid_decay"):
-            getattr(L, f).argtypes = [C.c_void_p]
-        L.ref_grid_allocate.argtypes = [C.c_void_p, D3, D3]
-        L.ref_grid_add_cloud.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.ref_grid_add_cloud_ns.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-        for f in ("ref_grid_fill_column", "ref_grid_clear_column"):
-            getattr(L, f).argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.ref_grid_fill_cell.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-        L.ref_grid_get_map.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_float), C.c_void_p]
-        L.ref_grid_get_map.restype = C.c_uint64
-        L.ref_grid_get_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
-        L.ref_grid_get_cloud.restype = C.c_uint64
-        self.L, self.D3 = L, D3
-        self.h = L.ref_grid_create(D3(*origin), D3(*dim), res)
-
-    def info(self):
-        dim = (C.c_int32 * 3)(); ori = (C.c_double * 3)(); res = C.c_float()
-        self.L.ref_grid_get_map(self.h, 0, dim, ori, C.byref(res), None)
-        return tuple(dim), tuple(ori), res.value
-
-    def allocate(self, dim, ori):
-        return bool(self.L.ref_grid_allocate(self.h, self.D3(*dim), self.D3(*ori)))
-
-    def clear(self, nx=None, ny=None):
-        self.L.ref_grid_clear(self.h) if nx is None else self.L.ref_grid_clear_column(self.h, nx, ny)
-
-    def fill(self, nx, ny, nz=None):
-        self.L.ref_grid_fill_column(self.h, nx, ny) if nz is None else self.L.ref_grid_fill_cell(self.h, nx, ny, nz)
-
-    def add_cloud(self, pts, ns=None):
-        p = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
-        if ns is None:
-            self.L.ref_grid_add_cloud(self.h, p.shape[0], p.ctypes.data)
-            return None
-        o = np.ascontiguousarray(ns, dtype=np.int32).reshape(-1, 3)
-        out = np.empty((max(p.shape[0] * o.shape[0], 1), 3), dtype=np.int32)
-        n = self.L.ref_grid_add_cloud_ns(self.h, p.shape[0], p.ctypes.data, o.shape[0], o.ctypes.data, out.ctypes.data, out.shape[0])
-        return out[:n]
-
-    def decay(self):
-        self.L.ref_grid_decay(self.h)
-
-    def get_map(self, inflated=False):
-        dim, _, _ = self.info()
-        data = np.empty(dim[0] * dim[1] * dim[2], dtype=np.int8)
-        d = (C.c_int32 * 3)(); o = (C.c_double * 3)(); r = C.c_float()
-        self.L.ref_grid_get_map(self.h, 1 if inflated else 0, d, o, C.byref(r), data.ctypes.data)
-        return data
-
-    def get_cloud(self):
-        n = int(self.L.ref_grid_get_cloud(self.h, None, 0))
-        out = np.empty((max(n, 1), 3), dtype=np.float64)
-        self.L.ref_grid_get_cloud(self.h, out.ctypes.data, n)
-        return out[:n]
 
 
 def _exercise(A, B, rng, same):
